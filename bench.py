@@ -16,11 +16,18 @@ of the final int32 tokens ends the job (weak scaling: 256 rows per GPU).
 
 Precision routes (include/hudiff_hip.h): the top level is the library's DEFAULT route -- split precision since round 4: every
 fp32 product of the large GEMMs and of the attention core as three fp16 MFMAs on fp16 (hi, lo) operand splits with fp32
-accumulation (`dtype` says so, `roofline.peak` = 2500 / 3 TFLOP/s fp32-equivalent).  `all_fp32_kernels` is the same workload
-with every product on the fp32 MFMA pipe, sampled as long as the top level (same --steps), with its own PMC passes and clock /
-power record: a strict reader grades that object.  `precision_evidence` holds, for this very run's rows and weights, each
-route's max |dlogit| against a float64 CPU evaluation at three points along the sample and the token agreement between the
-routes over ALL timed samples.
+accumulation (`dtype` says so, `roofline.peak` = 2500 / 3 TFLOP/s fp32-equivalent).
+
+A plain run times the metric's own leg only: set up, warm up, time --steps samples, print the line.  `--full` adds everything
+else the line can carry, each a run of its own after the timed region: `all_fp32_kernels` (the same workload with every
+product on the fp32 MFMA pipe, sampled as long as the top level, with its own PMC passes and clock / power record),
+`f32_gemm_route`, `precision_evidence` (for this very run's rows and weights, each route's max |dlogit| against a float64 CPU
+evaluation at three points along the sample and the token agreement between the routes over ALL timed samples), the HuDiff-Nb
+`secondary` line, the live PMC figures of `roofline` (traffic, hbm_gbps, mfma_busy) and `cpu_baseline`.
+
+`--dump-outputs DIR` writes what the timed path returned for its last sample -- the final tokens of every row, gathered over
+the ranks -- as DIR/tokens.npy (float32 [rows, L]).  Inputs, weights and noise keys depend only on the arguments, so two
+builds run with the same arguments can be compared output for output.
 
 Timed region: inputs already resident in HBM (hd_sample_begin uploaded them); K x [restore tokens
 device-side, re-key noise, run all T steps]; bracketed by barrier + device synchronise on both sides,
@@ -80,6 +87,11 @@ def parse():
                     "instead of T replays of the step graph")
     ap.add_argument("--lanes", type=int, default=2, choices=[1, 2],
                     help="2 = the batch runs as two concurrent half-batches on two streams (library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the other routes' legs, precision_evidence, the HuDiff-Nb secondary line, the live PMC passes and the "
+                         "CPU baseline after the timed region (the --no-* switches above pick among them); off: the metric's own leg only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final tokens of the last timed sample (all ranks' rows) to DIR/tokens.npy as float32")
     return ap.parse_args()
 
 
@@ -532,6 +544,22 @@ def attach_pmc(roof, pmc):
     roof["pmc_note"] = pmc["note"]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tokens):
+    """--dump-outputs: the final tokens of the last timed sample as DIR/tokens.npy, float32 (token ids are exact in it).  Beyond 64 MB
+    a fixed seeded sample of the rows is written, in row order, with their indices in DIR/tokens_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = np.asarray(tokens, dtype=np.float32)
+    max_rows = max(1, DUMP_LIMIT_BYTES // (out.shape[1] * out.itemsize + 8))
+    if out.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(out.shape[0], size=max_rows, replace=False))
+        out = out[rows]
+        np.save(os.path.join(out_dir, "tokens_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "tokens.npy"), out)
+
+
 def relaunch_one_rank_per_gpu(args):
     """`python bench.py --gpus N` without a launcher around it (the driver's single-node command shape): start N ranks of
     this very command under torch.distributed.run -- one process per GPU, rendezvous on 127.0.0.1 -- and hand back its exit
@@ -647,7 +675,7 @@ def main():
     tokens = model.sample_end()
     prec_main = model.precision_info()
     route_main = route_of(prec_main)
-    only_main = args.only_main or args.max_t > 0 or world > 1 or force_pg
+    only_main = not args.full or args.only_main or args.max_t > 0 or world > 1 or force_pg
     f32_gemm = secondary = None
     t_phase = time.perf_counter()
 
@@ -808,6 +836,8 @@ def main():
         filled = bool(((all_tokens >= 0) & (all_tokens <= 22)).all())
         if args.max_t == 0:
             assert not (all_tokens == 22).any(), "masked slots left after a full sample"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, all_tokens)
         seqs = n_gpus * B * args.steps
         value = seqs / elapsed
         raw_main = {"gpu_ms": gpu_ms, "steps": args.steps, "B": B, "Tmax": Tmax, "clock_power": clock_power}
@@ -850,7 +880,7 @@ def main():
         # HBM-side traffic, HBM GB/s and MFMA-busy per launch: live PMC passes of this very command (subprocess, after the timed region)
         # (N > 1: rank 0 profiles a single-rank run of the same per-GPU workload on its own GPU while the other ranks wait at the
         #  final barrier -- the ranks are independent, so its counters are every rank's)
-        pmc_wanted = args.pmc in ("auto", "live") and not args.only_main and args.max_t <= 0 and (not force_pg or world > 1)
+        pmc_wanted = args.full and args.pmc in ("auto", "live") and not args.only_main and args.max_t <= 0 and (not force_pg or world > 1)
         if pmc_wanted and (not only_main or world > 1):
             attach_pmc(out["roofline"], live_pmc(args, kind, mode, route_main))
             if world > 1 and "pmc_note" in out["roofline"]:
@@ -871,7 +901,7 @@ def main():
             out["secondary"] = {"hudiff_nb_configs3": secondary}
         if args.max_t > 0:
             out["truncated"] = f"--max-t {args.max_t}: NOT the metric (profiling run)"
-        if not args.no_cpu_baseline and n_gpus == 1 and not args.only_main:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1 and not args.only_main:
             out["cpu_baseline"] = cpu_baseline(kind, cfg, sd, mode, args.cpu_rows, args.cpu_steps, float(batch["T"].mean()),
                                                args.cpu_impl, args.data)
             phase("CPU baseline")

@@ -8,10 +8,10 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r05
 rm -rf $OUT; mkdir -p $OUT
-python $R/bench.py --steps 3 --warmup 1 2>$OUT/bench_ab.err | tail -1 > $OUT/bench_ab256.json
+python $R/bench.py --steps 3 --warmup 1 --full 2>$OUT/bench_ab.err | tail -1 > $OUT/bench_ab256.json
 grep "^\[bench\]" $OUT/bench_ab.err > $OUT/bench_ab256_phases.txt
-python $R/bench.py --kind nb --steps 3 --warmup 1 2>$OUT/bench_nb.err | tail -1 > $OUT/bench_nb256.json
-python $R/bench.py --kind nb --mode inpaint --steps 3 --warmup 1 --no-cpu-baseline --no-evidence 2>>$OUT/bench_nb.err | tail -1 > $OUT/bench_nb256_inpaint.json
+python $R/bench.py --kind nb --steps 3 --warmup 1 --full 2>$OUT/bench_nb.err | tail -1 > $OUT/bench_nb256.json
+python $R/bench.py --kind nb --mode inpaint --steps 3 --warmup 1 --full --no-cpu-baseline --no-evidence 2>>$OUT/bench_nb.err | tail -1 > $OUT/bench_nb256_inpaint.json
 prof() {   # name, kind, route, lanes, [ENV=VAL ...]
   name=$1; kind=$2; route=$3; lanes=$4; shift 4
   CMD="python $R/bench.py --kind $kind --steps 1 --warmup 0 --max-t 6 --no-cpu-baseline --lanes $lanes --pmc off --precision $route"

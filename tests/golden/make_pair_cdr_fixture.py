@@ -10,8 +10,9 @@ prove the built-in slotter equal to it, but a slotter that shifts a loop in eith
 slot-for-slot CDR identity collapses.
 
 Written (data only): the humanized partners slotted by hudiff_amd.numbering (int8 tokens [348, 291], chain type of the light
-chain), next to the mouse rows of hudiff_amd/data/real_rows.npz; and pair_cdr_review.json, the pairs an ANARCI run should
-look at first.  The identities themselves are recomputed by tests/test_numbering_pairs.py.
+chain), next to the mouse rows of hudiff_amd/data/real_rows.npz; their raw heavy / light sequences
+(huab348_humanized_partner_seqs.json, so that the slotting can be re-checked without the CSV); and pair_cdr_review.json,
+the pairs an ANARCI run should look at first.  The identities themselves are recomputed by tests/test_numbering_pairs.py.
 
 Yard-stick without any numbering: a Needleman-Wunsch alignment of the two raw chains.  A pair is a "graft pair" when >= 95 %
 of the mouse residues in Kabat-CDR slots are aligned to an identical partner residue; for such a pair the slot-for-slot CDR
@@ -30,6 +31,7 @@ from hudiff_amd.numbering import number_sequence_builtin  # noqa: E402
 
 CSV = "/root/reference/data/antibody_eval_data/HuAb348_data/humanization_pair_data_filter.csv"
 OUT = os.path.join(ROOT, "tests", "golden", "huab348_humanized_partners.npz")
+SEQS = os.path.join(ROOT, "tests", "golden", "huab348_humanized_partner_seqs.json")
 
 
 def nw_pairs(a, b):
@@ -83,11 +85,21 @@ def pair_cdr_numbers(mouse_tokens, human_tokens):
     return tot, slot_match / tot, same_res / tot, same_slot / tot
 
 
+def write_partner_sequences(human):
+    """Raw heavy / light chains of the humanized partners, in the row order of huab348_humanized_partners.npz."""
+    import json
+    json.dump({"source": "HuAb348 humanization_pair_data_filter.csv, rows with type != mouse, in file order",
+               "h_seq": [str(s) for s in human["h_seq"]], "l_seq": [str(s) for s in human["l_seq"]]},
+              open(SEQS, "w"), indent=0)
+    print(SEQS, os.path.getsize(SEQS) // 1024, "KiB")
+
+
 def main():
     df = pd.read_csv(CSV)
     mouse = df[df["type"] == "mouse"].reset_index(drop=True)
     human = df[df["type"] != "mouse"].reset_index(drop=True)
     assert len(mouse) == len(human) == 348
+    write_partner_sequences(human)
     toks, lch, names = [], [], []
     for m, h in zip(mouse.itertuples(), human.itertuples()):
         assert m.order_name.split("_")[0] == h.order_name.split("_")[0], (m.order_name, h.order_name)

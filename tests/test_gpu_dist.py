@@ -100,7 +100,7 @@ def test_bench_gpus_2_reports_rank_0_counters(tmp_path):
     """N > 1 lines carry HBM traffic / GB/s / MFMA-busy too (north_star: "rocprof-reported HBM GB/s and MFMA utilisation ... at
     1/2/4/8 GPUs"): rank 0 profiles a single-rank run of the per-GPU workload while the other rank waits at the final barrier."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "24",
-                        "--no-cpu-baseline"], env=_clean_env(HUDIFF_BENCH_SHARE_GPU="1"), cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=_clean_env(HUDIFF_BENCH_SHARE_GPU="1"), cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = _last_json(r.stdout)
     roof = line["roofline"]
@@ -111,7 +111,7 @@ def test_bench_gpus_2_reports_rank_0_counters(tmp_path):
 
 
 def test_default_bench_line_carries_the_measurement_contract(tmp_path):
-    """One default-shaped `python bench.py` run (smaller batch, bounded CPU leg): the single JSON line must hold everything the
+    """One `python bench.py --full` run (smaller batch, bounded CPU leg): the single JSON line must hold everything the
     measurement contract names -- metric / value / unit / n_gpus / steps / warmup / ms_per_step / dtype / config.workload; `roofline`
     with bound, achieved, peak, frac, traffic (live PMC), hbm_gbps and mfma_busy; `cpu_baseline` with value / cores / kind / sample.
     Round 4 (VERDICT r3 "Next" #2): the top level is the split route and says so (`dtype`, `precision_route`, peak 2500 / 3); the
@@ -121,7 +121,7 @@ def test_default_bench_line_carries_the_measurement_contract(tmp_path):
     for k in ("HUDIFF_X3", "HUDIFF_ATTN_X3", "HUDIFF_PRECISION"):       # the DEFAULT line is what is checked, also inside the nested f32_all re-run
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "64", "--steps", "2", "--warmup", "0",
-                        "--cpu-rows", "2", "--cpu-steps", "2", "--evidence-rows", "2"], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=1500)
+                        "--cpu-rows", "2", "--cpu-steps", "2", "--evidence-rows", "2", "--full"], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                      # ONE JSON line

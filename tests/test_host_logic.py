@@ -384,3 +384,28 @@ def test_bench_clock_power_sampler_is_optional():
         assert out is None or {"sclk_mhz_median", "power_w_median", "samples"} <= set(out)
     phys, logical = mod.physical_cores()
     assert 1 <= phys <= logical
+
+
+def test_bench_dump_outputs_writes_float32_tokens_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: the final tokens as DIR/tokens.npy in float32 (ids exact); above the size limit a fixed seeded
+    sample of the rows in row order, with the row indices beside it, the same on every call."""
+    import importlib.util
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(root, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--dump-outputs", str(tmp_path / "d")])
+    a = mod.parse()
+    assert a.steps == 3 and a.dump_outputs == str(tmp_path / "d") and a.full is False
+    tok = np.random.default_rng(1).integers(0, 22, size=(40, 291)).astype(np.int32)
+    mod.dump_outputs(str(tmp_path / "d"), tok)
+    got = np.load(tmp_path / "d" / "tokens.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, tok) and not (tmp_path / "d" / "tokens_rows.npy").exists()
+    monkeypatch.setattr(mod, "DUMP_LIMIT_BYTES", 10 * (291 * 4 + 8))
+    for sub in ("e", "f"):
+        mod.dump_outputs(str(tmp_path / sub), tok)
+    rows = np.load(tmp_path / "e" / "tokens_rows.npy")
+    got = np.load(tmp_path / "e" / "tokens.npy")
+    assert got.shape == (10, 291) and rows.dtype == np.float64 and (np.diff(rows) > 0).all()
+    assert np.array_equal(got, tok[rows.astype(np.int64)]) and np.array_equal(rows, np.load(tmp_path / "f" / "tokens_rows.npy"))

@@ -9,7 +9,6 @@ import os
 import sys
 
 import numpy as np
-import pytest
 
 from conftest import GOLDEN
 from hudiff_amd import evalsets as E
@@ -36,16 +35,15 @@ def test_humanized_partners_share_cdr_slots_with_their_mouse_antibodies():
     assert (slot_id <= nw_id + 1e-9).all()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data"), reason="reference data absent (GPU box)")
 def test_partner_fixture_is_what_the_slotter_gives_today():
-    import pandas as pd
+    """The stored partner tokens are what hudiff_amd.numbering makes of the humanized partners' raw chains today."""
     from hudiff_amd import inputs as I
     from hudiff_amd.numbering import number_sequence_builtin
-    df = pd.read_csv("/root/reference/data/antibody_eval_data/HuAb348_data/humanization_pair_data_filter.csv")
-    human = df[df["type"] != "mouse"].reset_index(drop=True)
+    seqs = json.load(open(os.path.join(GOLDEN, "huab348_humanized_partner_seqs.json")))
+    assert len(seqs["h_seq"]) == len(seqs["l_seq"]) == 348
     z = np.load(os.path.join(GOLDEN, "huab348_humanized_partners.npz"))
     for i in range(0, 348, 7):
-        h = human.iloc[i]
-        tok = np.array(I._TK.seq2idx(I.slot_residues(number_sequence_builtin(h.h_seq)[0], "H") +
-                                     I.slot_residues(number_sequence_builtin(h.l_seq)[0], "L")))
+        h_seq, l_seq = seqs["h_seq"][i], seqs["l_seq"][i]
+        tok = np.array(I._TK.seq2idx(I.slot_residues(number_sequence_builtin(h_seq)[0], "H") +
+                                     I.slot_residues(number_sequence_builtin(l_seq)[0], "L")))
         assert np.array_equal(tok, z["tokens"][i].astype(tok.dtype)), i
