@@ -17,6 +17,7 @@ HD_ABI_VERSION = 1
 HD_KIND_ANTIBODY, HD_KIND_NANOBODY = 0, 1
 HD_ACT_RELU, HD_ACT_GELU = 1, 2
 HD_DROPOUT_FAITHFUL, HD_DROPOUT_OFF, HD_DROPOUT_INJECT, HD_NO_GRAPH, HD_NO_PRUNE, HD_ONE_LANE, HD_LOOP_GRAPH = 0, 1, 2, 4, 8, 16, 32
+HD_RECORD_LOGP = 64
 HD_PRECISION_DEFAULT, HD_PRECISION_F32_GEMM, HD_PRECISION_F32_ALL, HD_PRECISION_SPLIT = 0, 1, 2, 3
 PRECISIONS = {"default": HD_PRECISION_DEFAULT, "split": HD_PRECISION_SPLIT, "f32_gemm": HD_PRECISION_F32_GEMM, "f32_all": HD_PRECISION_F32_ALL}
 PRECISION_NAMES = {HD_PRECISION_SPLIT: "split", HD_PRECISION_F32_GEMM: "f32_gemm", HD_PRECISION_F32_ALL: "f32_all", HD_PRECISION_DEFAULT: "default"}
@@ -28,6 +29,7 @@ EXPORTS = [
     "hd_last_run_ms", "hd_flops_per_row_forward", "hd_flops_per_row_sample_step", "hd_device_info", "hd_debug_stop_after", "hd_debug_read", "hd_precision_info",
     "hd_set_precision", "hd_precision_report", "hd_precision_reset", "hd_sample_tokens", "hd_debug_fail_next_lnsync",
     "hd_set_option", "hd_get_option", "hd_debug_scatter_lnsync",
+    "hd_sample_logp", "hd_score_begin", "hd_score",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -89,6 +91,10 @@ def load():
     lib.hd_sample_restart.argtypes = [vp, C.c_uint64]
     lib.hd_sample_end.argtypes = [vp, i32p]
     lib.hd_sample_tokens.argtypes = [vp, i32p]
+    score_args = [vp, i32p, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint64, u8p, u8p]
+    lib.hd_sample_logp.argtypes = [vp, f32p]
+    lib.hd_score_begin.argtypes = score_args
+    lib.hd_score.argtypes = score_args + [f32p]
     lib.hd_sync.argtypes = [vp]
     lib.hd_last_run_ms.argtypes = [vp, f32p, i32p]
     lib.hd_flops_per_row_forward.argtypes = [P(HdConfig)]

@@ -98,6 +98,21 @@ def load_numbered(path):
     return rows
 
 
+def write_logp_csv(path, rows, sweep=False):
+    """Sidecar of a sampling run (``--logp_fpath``): one line per SAMPLED row, 'name,pass,replica,T,logp,chosen' (with ``sweep``:
+    'name,sweep,pass,replica,T,logp,chosen').  T = slots the row sampled, logp = their total log-probability under the distributions
+    they were drawn from, chosen = 1 when the row was written to sample_humanization_result.csv."""
+    width = 7 if sweep else 6
+    with open(path, "w", encoding="UTF-8") as f:
+        f.write("name,sweep,pass,replica,T,logp,chosen\n" if sweep else "name,pass,replica,T,logp,chosen\n")
+        for row in rows:
+            if len(row) != width:
+                raise ValueError(f"a row of the log-probability sidecar has {width} fields, got {row!r}")
+            *head, T, logp, chosen = row
+            f.write(",".join(str(x) for x in head) + f",{int(T)},{float(logp):.6f},{int(chosen)}\n")
+    return path
+
+
 def write_fasta_2line(records, path):
     """[(id, description, sequence)] -> '>id description\\nSEQ' (the 'fasta-2line' flavour)."""
     with open(path, "w") as f:

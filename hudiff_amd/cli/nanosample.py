@@ -20,7 +20,8 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, noise_in_reference_order, sample_jobs_with_retry, seed_all
-from .common import add_runtime_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped
+from .common import (add_runtime_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
+                     write_logp_csv)
 
 
 def build_parser():
@@ -47,6 +48,11 @@ def build_parser():
     p.add_argument("--q_noise_fpath", type=str, default=None,
                    help="parity aid: .npz whose array 'q' [draws, batch_size, 22] is the torch.multinomial noise a run of the reference "
                         "recorded (input row by input row, step by step); replaces the library's counter-based noise for the first sweep")
+    p.add_argument("--logp_fpath", type=str, default=None,
+                   help="also write a CSV 'name,sweep,pass,replica,T,logp,chosen' with one line per sampled row of every sweep: logp = the "
+                        "row's total log-probability under the distributions that sweep drew from -- a re-sweep's value is that sweep's "
+                        "draws GIVEN the already filled tokens, not the likelihood of the sequence; chosen = 1 for the rows written to "
+                        "sample_humanization_result.csv (which stays byte-identical)")
     add_runtime_args(p)
     return p
 
@@ -114,11 +120,15 @@ def main(argv=None):
             logger.info(I.untokenize_nanobody(row))
             logger.info("Need to re sample again.")
     q_noise = noise_in_reference_order(np.load(args.q_noise_fpath)["q"], jobs, args.batch_size) if args.q_noise_fpath else None
+    records = [] if args.logp_fpath else None
+    more = {} if records is None else {"logp_records": records}
     written = sample_jobs_with_retry(model, jobs, args.batch_size, args.seed, want=args.sample_number,
                                      tries=args.try_number, accept=lambda row: chain_is_valid(I.untokenize_nanobody(row)),
-                                     device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise)
+                                     device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise, **more)
     if rank != 0:
         return None
+    if records is not None:
+        write_logp_csv(args.logp_fpath, [(jobs[j].name, sweep, 0, r, T, lp, ch) for j, sweep, r, T, lp, ch in sorted(records)], sweep=True)
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")
     human = []
     with open(save_fpath, "a", encoding="UTF-8") as f:

@@ -27,7 +27,8 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, noise_in_reference_order, sample_jobs, seed_all
-from .common import add_runtime_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line
+from .common import (add_runtime_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
+                     write_logp_csv)
 
 
 def build_parser():
@@ -65,6 +66,10 @@ def build_parser():
     p.add_argument("--q_noise_fpath", type=str, default=None,
                    help="parity aid: .npz whose array 'q' [draws, batch_size, 22] is the torch.multinomial noise a run of the reference "
                         "recorded (input row by input row, step by step); replaces the library's counter-based noise for the first pass")
+    p.add_argument("--logp_fpath", type=str, default=None,
+                   help="also write a CSV 'name,pass,replica,T,logp,chosen' with one line per sampled row: logp = the row's total "
+                        "log-probability under the distributions its tokens were drawn from, chosen = 1 for the rows written to "
+                        "sample_humanization_result.csv (which stays byte-identical)")
     add_runtime_args(p)
     return p
 
@@ -211,10 +216,14 @@ def main(argv=None):
             if passes != 1:
                 raise ValueError("--q_noise_fpath holds the noise of ONE pass over the input rows")
             q_noise = noise_in_reference_order(np.load(args.q_noise_fpath)["q"], jobs, args.batch_size)
+        more = {"return_logp": True} if args.logp_fpath else {}
         result = sample_jobs(model, jobs, args.batch_size, args.seed, passes=passes, device_batch=args.device_batch,
-                             dropout=args.dropout, q_noise=q_noise)
+                             dropout=args.dropout, q_noise=q_noise, **more)
+        if args.logp_fpath:
+            result, result_logp = result
     if rank != 0:
         return None
+    chosen = set()                                                  # (job, pass, replica) of the rows written below
 
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")
     human_rows = []
@@ -227,6 +236,7 @@ def main(argv=None):
                 if args.sample_number <= 0:
                     continue
                 r = select_most_similar(job.parent["tokens"], result[j, 0])
+                chosen.add((j, 0, r))
                 g_h, g_l = I.untokenize_antibody(result[j, 0, r])
                 f.write(f"humanization,{sample_name},{g_h},{g_l}\n")
                 human_rows.append((g_h, g_l))
@@ -237,9 +247,13 @@ def main(argv=None):
                         if left == 0:
                             break
                         g_h, g_l = I.untokenize_antibody(result[j, p, r])
+                        chosen.add((j, p, r))
                         f.write(f"humanization,{sample_name},{g_h},{g_l}\n")
                         human_rows.append((g_h, g_l))
                         left -= 1
+    if args.logp_fpath:
+        write_logp_csv(args.logp_fpath, [(job.name, p, r, len(job.loc), float(result_logp[j, p, r].astype(np.float64).sum()), (j, p, r) in chosen)
+                                         for j, job in enumerate(jobs) for p in range(result.shape[1]) for r in range(args.batch_size)])
     logger.info("Length did not equal list: {}".format([]))
     logger.info("Wrong idx: {}".format([]))
     # sample_identity.fa (trans_to_chain + save_pairs, sample.py:34-54): '{fa_version}human{i}' VH / VL pairs

@@ -94,6 +94,9 @@ struct Workspace {
     float *PW = nullptr, *YV = nullptr;                      // pruned last block: p_j rstd_j [B, nhead, 320], weighted input rows [B, nhead, D]
     int32_t *tokens = nullptr, *tokens0 = nullptr, *region = nullptr, *chain = nullptr, *order = nullptr, *T = nullptr;
     int capT = 0;
+    // [B, Tmax] beside `order` (same capacity, regrown together): log-probability of the token written by row b at step t (recording
+    // and scoring sessions), and the token a scoring session forces there
+    float* logp = nullptr; int32_t* target = nullptr;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -206,6 +209,7 @@ struct HdModel {
         int graph_B = -1; uint32_t graph_flags = 0; int graph_drop = -1; bool graph_q = false; int graph_Tmax = -1;
         int graph_qB = -1, graph_qoff = -1;
         int graph_x3 = -1;                           // kernel_set() when the graph was captured (split kernels in use, ln_sync level)
+        int graph_mode = -1;                         // draw mode of the captured step (DRAW_SAMPLE / DRAW_RECORD / DRAW_SCORE)
         const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
         // the T-step loop as ONE graph: `loop_steps` child-graph nodes of `graph` in a chain (hd_sample_run)
         hipGraph_t loop_graph = nullptr;
@@ -231,6 +235,8 @@ struct HdModel {
     int s_steps = 0;                                 // steps enqueued since then (largest t1 of hd_sample_run)
     uint32_t sflags = 0;
     bool s_has_q = false;
+    int s_mode = DRAW_SAMPLE;                        // draw stage of the session: plain, recording (HD_RECORD_LOGP), teacher-forced (hd_score_begin)
+    bool logp_ready = false;                         // the lanes' logp buffers hold a finished recording session (hd_sample_logp after the end)
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
     int debug_stop_after = 0;     // 0 = run everything (hd_debug_stop_after)
@@ -1661,6 +1667,7 @@ extern "C" HdStatus hd_forward(HdModel* m, const int32_t* tokens, const int32_t*
     if (!m || !tokens || !region || !logits) return fail(HD_ERR_INVALID, "hd_forward: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_forward: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_forward: a sampling session is open (hd_sample_end it first)");
+    m->logp_ready = false;                           // (lane 0's workspace may be regrown below)
     if (B < 0) return fail(HD_ERR_INVALID, "hd_forward: B = %d", B);
     if (B == 0) return HD_OK;
     HIP_TRY(hipSetDevice(m->device));
@@ -1710,8 +1717,17 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
     Workspace& ws = ln.ws;
     // the injected Exp(1) noise lives once, for the whole batch, in the model (m->qnoise)
     // (the last workgroup of sample_step_k advances the step)
-    hipLaunchKernelGGL(sample_step_k, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, prune ? ws.Xc : ws.Y, m->D, m->head, ws.tokens, ws.order,
-                       ws.T, m->sTmax, m->s_has_q ? m->qnoise : nullptr, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1);
+    const float* hm = prune ? ws.Xc : ws.Y;
+    const float* qn = m->s_has_q ? m->qnoise : nullptr;
+    if (m->s_mode == DRAW_SAMPLE)
+        hipLaunchKernelGGL(sample_step_k, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
+                           ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1);
+    else if (m->s_mode == DRAW_RECORD)
+        hipLaunchKernelGGL(sample_step_logp_k<DRAW_RECORD>, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
+                           ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1, ws.logp, (const int32_t*)ws.target);
+    else
+        hipLaunchKernelGGL(sample_step_logp_k<DRAW_SCORE>, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
+                           ws.T, m->sTmax, (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1, ws.logp, (const int32_t*)ws.target);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -1719,7 +1735,7 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
 static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                   uint64_t seed, uint64_t row0, const float* q_noise,
-                                  const uint8_t* enc_masks, const uint8_t* conv_masks) {
+                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score) {
     if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -1728,6 +1744,8 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->sB = B; m->sTmax = Tmax; m->sflags = flags; m->s_has_q = q_noise != nullptr; m->timed = false; m->last_steps = 0;
     m->s_seed = seed; m->s_steps = 0; m->s_dirty = false;
     m->nlanes = 1; m->cl = 0;
+    m->s_mode = score ? DRAW_SCORE : (flags & HD_RECORD_LOGP) ? DRAW_RECORD : DRAW_SAMPLE;
+    m->logp_ready = false;
     if (B == 0) { m->in_session = true; return HD_OK; }
     HD_TRY(validate_inputs(m, tokens, region, chain, B));
     for (int b = 0; b < B; ++b) {
@@ -1736,6 +1754,21 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
             int s = order[(size_t)b * Tmax + t];
             if (s < 0 || s >= m->L) return fail(HD_ERR_INVALID, "order[%d,%d] = %d out of [0,%d)", b, t, s, m->L);
         }
+    }
+    // scoring: the caller's tokens are complete; the slots to score become the targets and are masked in the library's copy
+    std::vector<int32_t> masked, target;
+    if (score) {
+        masked.assign(tokens, tokens + (size_t)B * m->L);
+        target.assign((size_t)B * (Tmax > 0 ? Tmax : 1), 0);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < T[b]; ++t) {
+                const int s = order[(size_t)b * Tmax + t], x = tokens[(size_t)b * m->L + s];
+                if (x < 0 || x > 21) return fail(HD_ERR_INVALID, "hd_score_begin: token %d at row %d slot %d (step %d) is not a residue or gap in [0,21]", x, b, s, t);
+                target[(size_t)b * Tmax + t] = x;
+            }
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < T[b]; ++t) masked[(size_t)b * m->L + order[(size_t)b * Tmax + t]] = 22;
+        tokens = masked.data();
     }
     const int dm = drop_mode_of(m, flags);
     if (dm == DROP_INJECT && (!enc_masks || !conv_masks)) return fail(HD_ERR_INVALID, "hd_sample_begin: HD_DROPOUT_INJECT needs masks");
@@ -1768,21 +1801,29 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
         {
             const size_t need = (size_t)Bl * (Tmax > 0 ? Tmax : 1);
             if (need > (size_t)ws.capT) {
-                if (ws.order) {                 // regrown: release the old buffer now, not at the next free_ws
-                    for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
-                        if (*it == (void*)ws.order) { ws.owned.erase(it); break; }
+                if (ws.order) {                 // regrown: release the old buffers now, not at the next free_ws
                     HIP_TRY(hipStreamSynchronize(ln.stream));
-                    hipFree(ws.order);
-                    ws.order = nullptr; ws.capT = 0;
-                    // a captured graph holds the old pointer
+                    for (void* old : {(void*)ws.order, (void*)ws.logp, (void*)ws.target}) {
+                        for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
+                            if (*it == old) { ws.owned.erase(it); break; }
+                        hipFree(old);
+                    }
+                    ws.order = nullptr; ws.logp = nullptr; ws.target = nullptr; ws.capT = 0;
+                    // a captured graph holds the old pointers
                     ln.drop_graphs();
                 }
                 HD_TRY(dalloc(ws, &ws.order, need));
+                HD_TRY(dalloc(ws, &ws.logp, need));
+                HD_TRY(dalloc(ws, &ws.target, need));
                 ws.capT = (int)need;
             }
         }
         if (Tmax > 0) HIP_TRY(hipMemcpyAsync(ws.order, order + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
         HIP_TRY(hipMemcpyAsync(ws.T, T + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+        if (m->s_mode != DRAW_SAMPLE && Tmax > 0) {
+            HIP_TRY(hipMemsetAsync(ws.logp, 0, (size_t)Bl * Tmax * sizeof(float), ln.stream));
+            if (score) HIP_TRY(hipMemcpyAsync(ws.target, target.data() + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+        }
         if (l == 0 && q_noise && Tmax > 0) {
             const size_t n = (size_t)Tmax * B * 22;
             if (n > m->qnoise_cap) {
@@ -1815,9 +1856,21 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
                                     const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                     uint64_t seed, uint64_t row0, const float* q_noise,
                                     const uint8_t* enc_masks, const uint8_t* conv_masks) {
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false);
     if (s != HD_OK && m && !m->in_session) {     // a failure half-way through the lane loop must not leave lane state behind
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false;
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE;
+    }
+    return s;
+}
+
+// A teacher-forced recording session (include/hudiff_hip.h "likelihood scoring"): hd_sample_begin on the library's masked copy of the
+// tokens, with the draw stage forced to the caller's own tokens.
+extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
+                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
+                                   uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks) {
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true);
+    if (s != HD_OK && m && !m->in_session) {
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE;
     }
     return s;
 }
@@ -1834,6 +1887,7 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         m->cl = l;
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+        if (m->s_mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
         HD_TRY(set_run_state(m, seed, m->s_row0 + (uint64_t)ln.row_off, 0));
     }
     m->cl = 0;
@@ -1857,7 +1911,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         const uint32_t gflags = m->sflags & HD_NO_PRUNE;
         if (!ln.graph_exec || ln.graph_B != ln.B || ln.graph_flags != gflags || ln.graph_drop != dm || ln.graph_q != m->s_has_q ||
             ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
-            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m)) {
+            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode) {
             ln.drop_graphs();
             HIP_TRY(hipStreamSynchronize(ln.stream));
             HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
@@ -1868,7 +1922,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             HIP_TRY(hipGraphInstantiate(&ln.graph_exec, ln.graph, nullptr, nullptr, 0));
             ln.graph_B = ln.B; ln.graph_flags = gflags; ln.graph_drop = dm; ln.graph_q = m->s_has_q; ln.graph_Tmax = m->sTmax;
             ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
-            ln.graph_x3 = kernel_set(m);
+            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode;
         }
     }
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipEventRecord(m->lane[l].ev0, m->lane[l].stream));
@@ -1968,7 +2022,7 @@ static HdStatus sample_end_impl(HdModel* m, int32_t* tokens, bool* numeric) {
 
 extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_end: no open session");
-    if (m->sB == 0) { m->in_session = false; return HD_OK; }
+    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s_mode != DRAW_SAMPLE; return HD_OK; }
     if (!tokens) { m->in_session = false; return fail(HD_ERR_INVALID, "hd_sample_end: null tokens"); }
     bool numeric = false;
     const HdStatus s = sample_end_impl(m, tokens, &numeric);
@@ -1976,6 +2030,7 @@ extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     m->s_dirty = false;
     m->cl = 0;
     if (s != HD_OK) return s;
+    m->logp_ready = m->s_mode != DRAW_SAMPLE;        // hd_sample_logp stays legal until the next begin / hd_forward
     if (numeric)
         return fail(HD_ERR_NUMERIC, "hd_sample: non-finite logits (NaN / inf) at some denoiser step -- weights or inputs out of range; "
                                     "the reference's torch.multinomial raises at this point");
@@ -2051,6 +2106,43 @@ extern "C" HdStatus hd_sample(HdModel* m, int32_t* tokens, const int32_t* region
     HdStatus s = hd_sample_run(m, 0, tmax_eff);
     if (s != HD_OK) { m->in_session = false; m->cl = 0; return s; }
     return hd_sample_end(m, tokens);
+}
+
+extern "C" HdStatus hd_sample_logp(HdModel* m, float* logp) {
+    if (!m || (!m->in_session && !m->logp_ready)) return fail(HD_ERR_STATE, "hd_sample_logp: no recording session (open, or ended and not yet replaced)");
+    if (m->s_mode == DRAW_SAMPLE) return fail(HD_ERR_STATE, "hd_sample_logp: the session does not record (HD_RECORD_LOGP / hd_score_begin)");
+    if (m->sB == 0 || m->sTmax == 0) return HD_OK;
+    if (!logp) return fail(HD_ERR_INVALID, "hd_sample_logp: null logp");
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(logp + (size_t)ln.row_off * m->sTmax, ln.ws.logp, (size_t)ln.B * m->sTmax * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
+    }
+    if (m->in_session) {
+        if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
+        else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+        if (m->s_dirty) return fail(HD_ERR_STATE, "hd_sample_logp: a guard of the split-precision kernels fired during these steps; their values "
+                                                   "are invalid (hd_sample_end repeats the sample)");
+    } else {
+        for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+    }
+    return HD_OK;
+}
+
+extern "C" HdStatus hd_score(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
+                             const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
+                             uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks, float* logp) {
+    if (m && !logp && B > 0 && Tmax > 0) return fail(HD_ERR_INVALID, "hd_score: null logp");
+    HD_TRY(hd_score_begin(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, enc_masks, conv_masks));
+    HdStatus s = hd_sample_run(m, 0, Tmax);
+    if (s != HD_OK) { m->in_session = false; m->cl = 0; return s; }
+    std::vector<int32_t> filled((size_t)B * m->L + 1);
+    s = hd_sample_end(m, filled.data());
+    if (s != HD_OK && s != HD_ERR_NUMERIC) return s;
+    const std::string msg = g_err;                   // (HD_ERR_NUMERIC: the values are still returned, as hd_sample returns its tokens)
+    HD_TRY(hd_sample_logp(m, logp));
+    if (s == HD_ERR_NUMERIC) return fail(HD_ERR_NUMERIC, "%s", msg.c_str());
+    return HD_OK;
 }
 
 extern "C" HdStatus hd_last_run_ms(HdModel* m, float* ms, int32_t* steps) {

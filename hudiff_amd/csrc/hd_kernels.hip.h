@@ -2474,10 +2474,17 @@ __device__ __forceinline__ void ln_row_regs(const float* __restrict__ x, int D, 
 // NW waves per sequence: each normalises the row (the same arithmetic, so the same values) and takes the decoder rows
 // j = wave, wave + NW, ...; wave 0 then runs the softmax and the draw on the 22 logits (one wave per sequence with 22 serial
 // dot products was 103 us of latency per step).  x: the row (global or LDS); lg: 32 floats of LDS.  Called by every wave of the block.
-template <int NW>
+// MODE (compile time; DRAW_SAMPLE is what a plain sampling session launches):
+//   DRAW_RECORD  the same draw, and the log-probability of the drawn token goes to *logp_out
+//   DRAW_SCORE   teacher-forced: no noise and no argmax, the token is `target` (in [0, 22): checked by hd_score_begin) and its
+//                log-probability goes to *logp_out
+// log p_s = (logit_s - max) - log(sum_j exp(logit_j - max)): from the logits, not log(p), so a probability that underflowed in
+// e / esum still has a finite logarithm.
+enum { DRAW_SAMPLE = 0, DRAW_RECORD = 1, DRAW_SCORE = 2 };
+template <int NW, int MODE = DRAW_SAMPLE>
 __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w, int32_t* __restrict__ tokens, int b, int slot, uint32_t t,
                                            const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
-                                           float* lg) {
+                                           float* lg, float* __restrict__ logp_out = nullptr, int target = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float y[16];
     ln_row_regs(x, D, lane, w, y);
@@ -2501,6 +2508,14 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     // a NaN / infinite logit makes the sum NaN (the reference's torch.multinomial raises on such a row, sample.py:512); the
     // step still writes a token, hd_sample_end reports the flag
     if (lane == 0 && !(esum > 0.f && esum < INFINITY)) atomicOr(const_cast<uint32_t*>(&rs->pad[0]), 1u);
+    if constexpr (MODE == DRAW_SCORE) {
+        const float zt = __shfl(mylogit, target & 31);
+        if (lane == 0) {
+            tokens[(long)b * L + slot] = target;
+            *logp_out = (zt - mx) - logf(esum);
+        }
+        return;
+    }
     const float p = e / esum;
     float q = 1.f;
     if (lane < 22) {
@@ -2522,24 +2537,34 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
         if (r2 > ratio || (r2 == ratio && b2 < best)) { ratio = r2; best = b2; }
     }
     if (lane == 0) tokens[(long)b * L + slot] = best;
+    if constexpr (MODE == DRAW_RECORD) {
+        const float zb = __shfl(mylogit, best);          // (after the reduction every lane holds the winner)
+        if (lane == 0) *logp_out = (zb - mx) - logf(esum);
+    }
 }
 
 // advance != 0: the last workgroup to finish moves rs->step on (every thread of the grid has read it by then), which saves the
 // one-thread launch per step that advance_step_k was.
+// logp / target: [B, Tmax] of the lane (row b at step t), used by the recording and the teacher-forced kernel below only.
 constexpr int SS_WAVES = 16;
-__global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __restrict__ Hm, int D, HeadW w,
-                                                     int32_t* __restrict__ tokens,
-                                                     const int32_t* __restrict__ order,
-                                                     const int32_t* __restrict__ T, int Tmax,
-                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance) {
+template <int MODE>
+__device__ __forceinline__ void sample_step_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
+                                                 const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
+                                                 const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                 RunState* __restrict__ rs, const Segs& sg, int compact, int advance,
+                                                 float* __restrict__ logp, const int32_t* __restrict__ target) {
     __shared__ float lg[32];
     const int b = blockIdx.x;
     const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if ((int)t < T[b]) {
         const int slot = order[(long)b * Tmax + t];
         // compact: Hm is [B, D] holding only the visited row of each sequence (pruned last block)
-        sample_row<SS_WAVES>(Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
+        const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
+        if constexpr (MODE == DRAW_SAMPLE)
+            sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
+        else
+            sample_row<SS_WAVES, MODE>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg, logp + (long)b * Tmax + t,
+                                       MODE == DRAW_SCORE ? target[(long)b * Tmax + t] : 0);
     } else {
         __syncthreads();                                 // (sample_row has one: every wave has read the step before thread 0 goes on)
     }
@@ -2550,6 +2575,27 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __re
             __hip_atomic_store(&rs->step, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+__global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                     int32_t* __restrict__ tokens,
+                                                     const int32_t* __restrict__ order,
+                                                     const int32_t* __restrict__ T, int Tmax,
+                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance) {
+    sample_step_body<DRAW_SAMPLE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, nullptr, nullptr);
+}
+// The step of a recording (HD_RECORD_LOGP) or a teacher-forced (hd_score_begin) session: as sample_step_k, and logp[b, t] is written
+// for every row with t < T[b].
+template <int MODE>
+__global__ void __launch_bounds__(64 * SS_WAVES) sample_step_logp_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                     int32_t* __restrict__ tokens,
+                                                     const int32_t* __restrict__ order,
+                                                     const int32_t* __restrict__ T, int Tmax,
+                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance,
+                                                     float* __restrict__ logp, const int32_t* __restrict__ target) {
+    static_assert(MODE == DRAW_RECORD || MODE == DRAW_SCORE, "the plain draw is sample_step_k");
+    sample_step_body<MODE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target);
 }
 
 // Full decoder for hd_forward: logits[b, l, :] = Linear(LN(h[row(b,l)])) , one wave per (b, l).

@@ -215,11 +215,11 @@ class _Denoiser:
         return tok, reg, chn, B, was_torch
 
     @staticmethod
-    def _flags(dropout, graph=True, prune=True, lanes=2):
+    def _flags(dropout, graph=True, prune=True, lanes=2, record=False):
         f = {"faithful": L.HD_DROPOUT_FAITHFUL, "off": L.HD_DROPOUT_OFF, "inject": L.HD_DROPOUT_INJECT}[dropout]
         # graph: True = one hipGraph per step replayed T times, "loop" = the whole T-step loop as one hipGraph, False = eager
         return (f | (0 if graph else L.HD_NO_GRAPH) | (L.HD_LOOP_GRAPH if graph == "loop" else 0) | (0 if prune else L.HD_NO_PRUNE)
-                | (0 if lanes == 2 else L.HD_ONE_LANE))
+                | (0 if lanes == 2 else L.HD_ONE_LANE) | (L.HD_RECORD_LOGP if record else 0))
 
     def forward(self, H_L_seq, H_L_region_type, H_L_chn_type=None, *, dropout="faithful", seed=0, row0=0,
                 step=0, enc_masks=None, conv_masks=None):
@@ -255,30 +255,103 @@ class _Denoiser:
         return tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2):
-        """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens."""
+               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False):
+        """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
+
+        ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
+        log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
+        are the same with and without it."""
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
-                                    self._flags(dropout, graph, prune, lanes), int(seed), int(row0), L.ptr(q, C.c_float),
+                                    self._flags(dropout, graph, prune, lanes, bool(return_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
                                     L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8)))
         self._warn_on_guard()
+        logp = self.sample_logp(B, Tmax) if return_logp else None
         if was_torch:
             import torch
-            return torch.from_numpy(out.astype(np.int64))
-        return out
+            out = torch.from_numpy(out.astype(np.int64))
+            logp = None if logp is None else torch.from_numpy(logp)
+        return (out, logp) if return_logp else out
+
+    def sample_logp(self, B=None, Tmax=None):
+        """hd_sample_logp: logp float32 [B, Tmax] of the open session, or of the last one that recorded."""
+        B = self._session_B if B is None else B
+        Tmax = self._session_Tmax if Tmax is None else Tmax
+        logp = np.zeros((B, Tmax), dtype=np.float32)
+        L.check(self._lib.hd_sample_logp(self._h, L.ptr(logp, C.c_float)))
+        return logp
+
+    # -- likelihood of given sequences -------------------------------------------------------------
+    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm):
+        logp = np.zeros((B, Tmax), dtype=np.float32)
+        L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
+                                   L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
+                                   L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8), L.ptr(logp, C.c_float)))
+        self._warn_on_guard()
+        return logp
+
+    def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
+              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2):
+        """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
+        logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
+        one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
+
+        ``parallel``: the tokens are given, so the T steps of a row do not depend on each other: True expands every (row, step) to a
+        row of its own (scoring.expand_steps) and runs them as one-step device batches of at most ``device_batch`` rows; False runs
+        the sequential T-step loop (hd_score), which is what dropout needs -- generated masks are keyed by (row, step), which an
+        expanded row does not carry.  None: parallel when ``dropout == "off"``."""
+        if parallel is None:
+            parallel = dropout == "off"
+        if parallel and dropout != "off":
+            raise ValueError("step-parallel scoring needs dropout='off': dropout masks are keyed by (row, step), "
+                             "which an expanded row does not carry; use parallel=False")
+        tok, reg, chn, order, T, B, Tmax, _, em, cm, was_torch = self._sample_args(
+            tokens, region, chain, order, T, None, enc_masks, conv_masks)
+        flags = self._flags(dropout, graph, prune, lanes)
+        if not parallel:
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm)
+        else:
+            from . import scoring
+            x = scoring.expand_steps(tok, reg, chn, order, T)
+            n = x.tokens.shape[0]
+            # hd_score takes its targets from the tokens it is given (and masks the slot itself): hand each row its own target back
+            x.tokens[np.arange(n), x.order[:, 0]] = tok[x.rows, x.order[:, 0]]
+            flat = np.zeros(n, dtype=np.float32)
+            for s in range(0, n, int(device_batch)):
+                e = min(n, s + int(device_batch))
+                ch = None if x.chain is None else np.ascontiguousarray(np.concatenate([x.chain[s:e], x.chain[n + s:n + e]]))
+                flat[s:e] = self._score_seq(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
+                                            np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, 1, flags,
+                                            seed, 0, None, None)[:, 0]
+            logp = x.fold(flat, Tmax)
+        if was_torch:
+            import torch
+            return torch.from_numpy(logp)
+        return logp
+
+    def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
+                    graph=True, prune=True, lanes=2):
+        """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
+        last_run_ms / sample_logp work on it as on a sampling session."""
+        tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
+        L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
+                                         L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
+                                         self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
+                                         L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8)))
+        self._session_B, self._session_Tmax = B, Tmax
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2):
+                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
-                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0), L.ptr(q, C.c_float),
+                                          self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
                                           L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8)))
-        self._session_B = B
+        self._session_B, self._session_Tmax = B, Tmax
 
     def sample_run(self, t0, t1):
         L.check(self._lib.hd_sample_run(self._h, int(t0), int(t1)))

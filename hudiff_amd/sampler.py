@@ -49,13 +49,16 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
-                job_ids: Optional[Sequence[int]] = None) -> np.ndarray:
+                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
 
     ``job_ids``: the id each job's noise is keyed by (default: its position in ``jobs``).  Row (job, replica) draws
-    its noise as global row ``job_ids[job] * replicas + replica``, whatever else is in the batch."""
+    its noise as global row ``job_ids[job] * replicas + replica``, whatever else is in the batch.
+
+    ``return_logp``: also returns float32 [len(jobs), passes, replicas, Tmax], the log-probability of the token each row drew at
+    each step of each pass under the distribution it was drawn from (0 beyond a row's steps); gathered like the tokens."""
     L = model.max_len
     n_rows = len(jobs) * replicas
     rank, world, _ = D.env_rank_world()
@@ -63,6 +66,8 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     is_ab = model.kind == "ab"
     Tmax = max([len(j.loc) for j in jobs] + [1])
     out = np.zeros((passes, hi - lo, L), np.int32)
+    lp = np.zeros((passes, hi - lo, Tmax), np.float32) if return_logp else None
+    more = {"return_logp": True} if return_logp else {}
     jid = np.arange(len(jobs), dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
     pos = np.arange(lo, hi)                                      # positions in the packed (job-major) row list
     gids = jid[pos // replicas] * replicas + pos % replicas      # the ids the noise is keyed by
@@ -81,12 +86,20 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
         chain = np.array([j.chain[0] for j in jb] + [j.chain[1] for j in jb], np.int32) if is_ab else None
         for p in range(passes):
             tok = model.sample(tok, reg, chain, order, T, seed=seed + 1000003 * p, row0=int(gids[cs]), dropout=dropout,
-                               q_noise=None if q_noise is None else np.ascontiguousarray(q_noise[p][:Tmax, gids[cs:ce]]))
+                               q_noise=None if q_noise is None else np.ascontiguousarray(q_noise[p][:Tmax, gids[cs:ce]]), **more)
+            if return_logp:
+                tok, lp[p, s - lo:e - lo] = tok
             out[p, s - lo:e - lo] = tok
     gathered = [D.gather_rows(out[p], n_rows, L, all_ranks) for p in range(passes)]
+    # (the float32 bits of the log-probabilities travel as int32 through the same gather)
+    gathered_lp = [D.gather_rows(lp[p].view(np.int32), n_rows, Tmax, all_ranks) for p in range(passes)] if return_logp else None
     if gathered[0] is None:
-        return None
-    return np.stack(gathered, axis=0).reshape(passes, len(jobs), replicas, L).transpose(1, 0, 2, 3)
+        return (None, None) if return_logp else None
+    tokens = np.stack(gathered, axis=0).reshape(passes, len(jobs), replicas, L).transpose(1, 0, 2, 3)
+    if not return_logp:
+        return tokens
+    logp = np.ascontiguousarray(np.stack(gathered_lp, axis=0), dtype=np.int32).view(np.float32)
+    return tokens, logp.reshape(passes, len(jobs), replicas, Tmax).transpose(1, 0, 2, 3)
 
 
 def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.ndarray:
@@ -109,7 +122,8 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 
 
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
-                           device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None) -> List[List[np.ndarray]]:
+                           device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
+                           logp_records: Optional[list] = None) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -117,7 +131,11 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
     walks the replicas in order: stop when nothing is wanted; an accepted row is written and counted; a rejected
     row is written only when ``try_num == 1``; ``try_num`` drops by one per row looked at.  Here every sweep runs
     all still-active sequences as one device batch; the decisions are taken on every rank from all-gathered
-    tokens.  Returns, per job, the rows written, in order."""
+    tokens.  Returns, per job, the rows written, in order.
+
+    ``logp_records``: a list that receives one ``(job index, sweep, replica, T, logp, chosen)`` per sampled row -- logp = the
+    row's total log-probability under the distributions this sweep drew from (a re-sweep's value is that sweep's draws given the
+    already filled tokens), chosen = the row was written."""
     state = [{"left": want, "tries": tries, "tokens": None, "out": []} for _ in jobs]
     active = [j for j in range(len(jobs)) if want > 0 and tries > 0]
     sweep = 0
@@ -127,25 +145,34 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
         # noise is keyed by the ORIGINAL job index: a sequence's samples do not depend on which other inputs were
         # accepted earlier (or are in the file at all)
         # (q_noise: injected noise of sweep 0 only, [1, Tmax, len(jobs) * replicas, 22] keyed like the generated noise: parity runs)
+        more = {} if logp_records is None else {"return_logp": True}
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
-                          all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None)
+                          all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
+        if logp_records is not None:
+            res, res_lp = res
         still = []
         for a, j in enumerate(active):
             st = state[j]
             st["tokens"] = res[a, 0]
-            for row in res[a, 0]:
+            chosen = set()
+            for r, row in enumerate(res[a, 0]):
                 if st["left"] == 0:
                     break
                 ok = bool(accept(row))
                 if ok:
                     st["out"].append(row)
                     st["left"] -= 1
+                    chosen.add(r)
                 else:
                     if st["tries"] == 1:
                         st["out"].append(row)
+                        chosen.add(r)
                     if log is not None:
                         log(jobs[j], row)
                 st["tries"] -= 1
+            if logp_records is not None:
+                for r in range(res.shape[2]):
+                    logp_records.append((j, sweep, r, len(jobs[j].loc), float(res_lp[a, 0, r].astype(np.float64).sum()), int(r in chosen)))
             if st["left"] > 0 and st["tries"] > 0:
                 still.append(j)
         active = still

@@ -1,0 +1,129 @@
+"""Likelihood of given sequences under the denoiser (host side; the device side is hd_score, include/hudiff_hip.h).
+
+The network is an order-agnostic autoregressive model: for a visiting order sigma of the scored slots,
+``sum_t log p(x_sigma(t) | x_sigma(<t), everything outside the scored slots)`` is a one-order estimate of the log-likelihood of
+those slots, and the training objective is its mean over orders.  The tokens are given, so step t of a row does not depend on
+step t - 1: the T steps of one sequence are T independent forwards (``expand_steps``) that fill one device batch instead of T
+latency-bound launches of a single row.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import dist as D
+
+MASK_TOKEN = 22
+
+
+@dataclass
+class Expanded:
+    """Rows of ``expand_steps``: row i is (source row ``rows[i]``, step ``steps[i]``)."""
+    tokens: np.ndarray                   # [N, L] int32
+    region: np.ndarray                   # [N, L] int32
+    chain: Optional[np.ndarray]          # [2N] int32 (heavy ids, then light ids) or None
+    order: np.ndarray                    # [N, 1] int32: the slot the row scores
+    T: np.ndarray                        # [N] int32, all 1
+    rows: np.ndarray                     # [N] source row b
+    steps: np.ndarray                    # [N] step t of the source row
+    B: int                               # source rows
+
+    def fold(self, flat, Tmax: int) -> np.ndarray:
+        """Flat per-row values [N] -> [B, Tmax] float32, 0 where t >= T[b]."""
+        out = np.zeros((self.B, Tmax), np.float32)
+        out[self.rows, self.steps] = np.asarray(flat, np.float32).reshape(-1)
+        return out
+
+
+def expand_steps(tokens, region, chain, order, T) -> Expanded:
+    """Every (b, t < T[b]) becomes one row: the complete tokens of row b with ``order[b, t:T[b]]`` masked, row b's region and
+    chain ids, order ``[order[b, t]]`` and T = 1.  Rows are b-major, t ascending."""
+    tokens = np.asarray(tokens, np.int32)
+    region = np.asarray(region, np.int32)
+    T = np.asarray(T, np.int64).reshape(-1)
+    B, L = tokens.shape
+    order = np.asarray(order, np.int32)
+    # not reshape(B, -1): an empty batch (B = 0) leaves -1 undetermined
+    order = order.reshape(B, order.shape[1] if order.ndim == 2 else (order.size // B if B else 0))
+    if T.shape[0] != B or (T < 0).any() or (T > order.shape[1]).any():
+        raise ValueError(f"T must be [{B}] with 0 <= T[b] <= {order.shape[1]}")
+    rows = np.repeat(np.arange(B), T)
+    steps = np.concatenate([np.arange(t) for t in T] + [np.zeros(0, np.int64)]).astype(np.int64)
+    N = rows.shape[0]
+    tok = tokens[rows].copy()
+    slot = order[rows, steps] if N else np.zeros(0, np.int32)
+    # row (b, t) masks order[b, u] for t <= u < T[b]
+    at = 0
+    for b in range(B):
+        n = int(T[b])
+        for t in range(n):
+            tok[at + t, order[b, t:n]] = MASK_TOKEN
+        at += n
+    ch = None
+    if chain is not None:
+        chain = np.asarray(chain, np.int32).reshape(-1)
+        if chain.shape[0] != 2 * B:
+            raise ValueError(f"chain must be [{2 * B}] (heavy ids, then light ids)")
+        ch = np.concatenate([chain[:B][rows], chain[B:][rows]]).astype(np.int32)
+    return Expanded(tokens=tok, region=region[rows].copy(), chain=ch, order=slot.reshape(N, 1).astype(np.int32),
+                    T=np.ones(N, np.int32), rows=rows, steps=steps, B=B)
+
+
+def draw_orders(loc, orders: int, seed: int, job_id: int) -> np.ndarray:
+    """``orders`` visiting orders of the slots ``loc`` -> [orders, len(loc)]; a function of (seed, job_id, k) alone, so the orders
+    of a job do not depend on what else is scored or on how rows are sharded."""
+    loc = np.asarray(loc, np.int32)
+    out = np.empty((orders, len(loc)), np.int32)
+    for k in range(orders):
+        out[k] = np.random.default_rng([int(seed), int(job_id), k]).permutation(loc)
+    return out
+
+
+def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout: str = "off", parallel=None,
+               device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None):
+    """Score every job along ``orders`` random visiting orders of its ``loc``.
+
+    ``Job.tokens`` are COMPLETE sequences here (sampler.Job; ``loc`` = the slots to score, ``region`` / ``chain`` as for sampling).
+    Row (job j, order k) is global row ``job_ids[j] * orders + k`` (dropout masks are keyed by it); rows shard over ranks and are
+    gathered once.  Returns on rank 0 (every rank when single-process or ``all_ranks``; None elsewhere) a dict:
+      total [J, orders] float64   sum_t logp of each order        T [J]                scored slots
+      mean, std [J]               over the orders (std 0 for one)  per_residue [J]      mean / T (0 when T = 0)
+      logp [J, orders, Tmax] float32 per step, order [J, orders, Tmax] int32 the slot of each step (0-padded)."""
+    if orders < 1:
+        raise ValueError("orders must be >= 1")
+    J = len(jobs)
+    n_rows = J * orders
+    rank, world, _ = D.env_rank_world()
+    lo, hi = D.shard_bounds(n_rows, rank, world)
+    is_ab = model.kind == "ab"
+    Tmax = max([len(j.loc) for j in jobs] + [1])
+    jid = np.arange(J, dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
+    all_order = np.zeros((J, orders, Tmax), np.int32)
+    for j, job in enumerate(jobs):
+        all_order[j, :, :len(job.loc)] = draw_orders(job.loc, orders, seed, int(jid[j]))
+    out = np.zeros((hi - lo, Tmax), np.float32)
+    from .sampler import _id_runs
+    pos = np.arange(lo, hi)
+    gids = jid[pos // orders] * orders + pos % orders
+    for cs, ce in _id_runs(gids, device_batch):
+        ids = pos[cs:ce]
+        jb = [jobs[i // orders] for i in ids]
+        tok = np.stack([np.asarray(j.tokens) for j in jb]).astype(np.int32)
+        reg = np.stack([j.region for j in jb]).astype(np.int32)
+        order = np.stack([all_order[i // orders, i % orders] for i in ids])
+        T = np.array([len(j.loc) for j in jb], np.int32)
+        chain = np.array([j.chain[0] for j in jb] + [j.chain[1] for j in jb], np.int32) if is_ab else None
+        out[cs:ce] = model.score(tok, reg, chain, order, T, dropout=dropout, parallel=parallel, device_batch=device_batch,
+                                 seed=seed, row0=int(gids[cs]))
+    # one gather, as for the tokens: the float32 bits travel as int32
+    got = D.gather_rows(out.view(np.int32), n_rows, Tmax, all_ranks)
+    if got is None:
+        return None
+    logp = np.ascontiguousarray(got, dtype=np.int32).view(np.float32).reshape(J, orders, Tmax)
+    T = np.array([len(j.loc) for j in jobs], np.int64)
+    total = logp.astype(np.float64).sum(axis=2)
+    mean = total.mean(axis=1)
+    return {"total": total, "mean": mean, "std": total.std(axis=1), "per_residue": np.where(T > 0, mean / np.maximum(T, 1), 0.0),
+            "T": T, "logp": logp, "order": all_order}

@@ -48,7 +48,8 @@ extern "C" {
 #endif
 
 #define HD_ABI_VERSION 1      /* layout of HdConfig; rounds 4-5 added entry points only (hd_set_precision, hd_precision_report, hd_precision_reset,
-                                 hd_set_option, hd_get_option, hd_debug_scatter_lnsync) */
+                                 hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
+                                 hd_score and the flag HD_RECORD_LOGP */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -75,9 +76,11 @@ enum {
                                   does) instead of only for the row each sequence visits at that step      */
     HD_ONE_LANE         = 16u, /* hd_sample: keep the batch on one stream (default: batches >= 16 rows are
                                   split into two halves that run concurrently on two streams)              */
-    HD_LOOP_GRAPH       = 32u  /* hd_sample / hd_sample_run: the whole T-step loop of a lane is ONE hipGraph (a chain
+    HD_LOOP_GRAPH       = 32u, /* hd_sample / hd_sample_run: the whole T-step loop of a lane is ONE hipGraph (a chain
                                   of T child-graph nodes of the captured step) launched once, instead of T replays
                                   of the step graph (same results; measured 2.4 % slower on MI355X) */
+    HD_RECORD_LOGP      = 64u  /* hd_sample / hd_sample_begin: the session records the log-probability of every token it writes
+                                  (hd_sample_logp); the drawn tokens are the same with and without the flag             */
 };
 
 /* Hyper-parameters: the `model:` section of configs/antibody_train.yml:3-24 / heavy_train.yml:3-21,
@@ -159,6 +162,34 @@ HdStatus hd_sync(HdModel* m);
  * precision routes over all timed samples).  A guard that fired (see "precision routes") makes this fail with HD_ERR_STATE --
  * only hd_sample_end repeats a sample. */
 HdStatus hd_sample_tokens(HdModel* m, int32_t* tokens);
+
+/* ---- likelihood scoring ---------------------------------------------------------------------------
+ * The draw stage of a step is the only place where the step's distribution p = softmax(logits[slot, 0:22]) exists.  A RECORDING
+ * session (HD_RECORD_LOGP) keeps, for row b at step t < T[b], the log-probability of the token s it wrote there,
+ *     logp[b, t] = (logit_s - max_j logit_j) - log(sum_j exp(logit_j - max_j logit_j))        (fp32, from the logits, not log(p)),
+ * under the distribution the token was drawn from (so under the dropout masks of that step when dropout is active).
+ *
+ * hd_sample_logp copies logp [B, Tmax] of the session out, rows in whole-batch order whatever the lane split; entries with
+ * t >= T[b] are 0 (so are steps not run yet).  Legal inside an open session -- it synchronises, and fails with HD_ERR_STATE after a
+ * guard has fired, like hd_sample_tokens -- and after hd_sample / hd_sample_end until the next hd_sample_begin / hd_score_begin /
+ * hd_forward / hd_destroy.  A session that did not record -> HD_ERR_STATE.  The range guard and the ln_sync guard repeat a
+ * recording session like any other; the values then come from the repeat.
+ *
+ * hd_score_begin opens a TEACHER-FORCED recording session on sequences the caller already has: `tokens` [B, L] are complete,
+ * the library takes target[b, t] = tokens[b, order[b, t]] for t < T[b] (a target outside [0, 21] -> HD_ERR_INVALID), masks those
+ * slots to 22 in its own copy, and every step writes its target instead of drawing: no noise is read or generated, and
+ * logp[b, t] = log p(target | the slots that are not masked at step t).  sum_t logp[b, t] is the order-agnostic log-likelihood
+ * of the scored slots along the ONE visiting order given (the quantity the network was trained on is its mean over orders).
+ * hd_sample_run, hd_sample_restart, hd_sync, hd_sample_end (returns the re-filled tokens = the input), hd_sample_tokens,
+ * hd_last_run_ms and hd_sample_logp work on that session as on a sampling one; dropout flags, seed / row0 (generated masks) and
+ * injected masks mean what they mean for hd_sample.  hd_score = begin + run(0, Tmax) + end + hd_sample_logp. */
+HdStatus hd_sample_logp(HdModel* m, float* logp /* [B, Tmax] */);
+HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
+                        const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
+                        uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks);
+HdStatus hd_score(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
+                  const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
+                  uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks, float* logp /* [B, Tmax] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
