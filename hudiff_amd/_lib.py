@@ -29,7 +29,7 @@ EXPORTS = [
     "hd_last_run_ms", "hd_flops_per_row_forward", "hd_flops_per_row_sample_step", "hd_device_info", "hd_debug_stop_after", "hd_debug_read", "hd_precision_info",
     "hd_set_precision", "hd_precision_report", "hd_precision_reset", "hd_sample_tokens", "hd_debug_fail_next_lnsync",
     "hd_set_option", "hd_get_option", "hd_debug_scatter_lnsync",
-    "hd_sample_logp", "hd_score_begin", "hd_score",
+    "hd_sample_logp", "hd_score_begin", "hd_score", "hd_debug_launch_tally",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -38,6 +38,16 @@ OPTIONS = {n: i for i, n in enumerate((
     "loader_waves", "tiny_stages", "small_stages", "small_stages3_max_grid", "attn_qsplit_max_grid", "attn_waves", "loop_graph",
     "prune_value_via_rows", "split_tile", "gemm_small_tiles", "store_nt", "split_layer_mask", "split_attn", "fused_attn", "fused_attn_min_grid",
     "bn_chain", "bn_chain_min_tiles"))}
+
+# launch tally (include/hudiff_hip.h, HdDebugKernel): the enum's names in order, lower case without the HD_DBG_ prefix
+DEBUG_KERNELS = (
+    "x3_256x256_s2", "x3_256x256_s2_conv", "x3_256x128_s3", "x3_256x128_s3_conv", "x3_128x128_plain", "x3_128x128_plain_conv",
+    "x3_128x128_lnsync", "x3_128x128_lnsync_conv", "x3_64x128_s2", "x3_64x128_s2_conv", "x3_64x128_s3", "x3_64x128_s3_conv",
+    "x3_32x128_s2", "x3_32x128_s2_conv", "x3_32x128_s3", "x3_32x128_s3_conv", "x3_32x128_s3_loaders", "x3_32x128_s3_loaders_conv",
+    "f32_128x128_bk16", "f32_128x128_bk32", "f32_64x128", "f32_32x128",
+    "qkv_attn_19", "qkv_attn_10", "attn_x3_19_w12", "attn_x3_19_w8", "attn_x3_10", "attn_f32", "attn_qsplit",
+    "tail_sliced", "tail_launches", "value_via_rows", "value_via_projection",
+    "sample_lanes_1", "sample_lanes_2", "sample_lanes_3", "sample_lanes_4", "loop_graph")
 
 
 class HdConfig(C.Structure):
@@ -110,6 +120,7 @@ def load():
     lib.hd_set_option.argtypes = [vp, C.c_int32, C.c_int64]
     lib.hd_get_option.argtypes = [vp, C.c_int32, P(C.c_int64)]
     lib.hd_debug_scatter_lnsync.argtypes = [vp, C.c_int32]
+    lib.hd_debug_launch_tally.argtypes = [vp, P(C.c_int64), C.c_int32]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

@@ -240,12 +240,14 @@ struct HdModel {
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
     int debug_stop_after = 0;     // 0 = run everything (hd_debug_stop_after)
+    int64_t tally[HD_DBG_COUNT] = {};   // hd_debug_launch_tally: launches issued per kernel choice (host side; tests only)
     bool debug_lnsync_fail = false;   // hd_debug_fail_next_lnsync: ln_sync meetings of the next call give up after one poll
 };
 
 // the lane (stream + workspace + graph) the helper functions currently address
 static inline HdModel::Lane& cur(HdModel* m) { return m->lane[m->cl]; }
 static inline const HdModel::Lane& cur(const HdModel* m) { return m->lane[m->cl]; }
+static inline void tally(HdModel* m, int id) { m->tally[id] += 1; }
 
 static int dilation_of(const HdConfig& c, int n) {
     int log2r = 0;
@@ -1023,9 +1025,11 @@ static void launch_gemm(HdModel* m, GemmP& p, bool conv, bool per_seg, int stats
         q.tiles_n = q.N / bn;
         dim3 grid(((q.tiles_m + 7) / 8) * 8 * q.tiles_n);
         if (shape == 512) {
+            tally(m, HD_DBG_X3_256X256_S2 + (conv ? 1 : 0));
             if (conv) hipLaunchKernelGGL((gemm_x3_k<256, 256, 2, 4, true, 2>), grid, dim3(512), 0, st, q);
             else hipLaunchKernelGGL((gemm_x3_k<256, 256, 2, 4, false, 2>), grid, dim3(512), 0, st, q);
         } else if (shape == 256) {
+            tally(m, HD_DBG_X3_256X128_S3 + (conv ? 1 : 0));
             if (conv) hipLaunchKernelGGL((gemm_x3_k<256, 128, 4, 2, true, 3>), grid, dim3(512), 0, st, q);
             else hipLaunchKernelGGL((gemm_x3_k<256, 128, 4, 2, false, 3>), grid, dim3(512), 0, st, q);
         } else if (shape == 32) {
@@ -1040,13 +1044,16 @@ static void launch_gemm(HdModel* m, GemmP& p, bool conv, bool per_seg, int stats
             // fit one per CU (B = 16 on two lanes: 52.3 -> 49.5 otherwise).  HD_OPT_LOADER_WAVES = 0 switches them off.
             const int loaders = (int)m->opt[HD_OPT_LOADER_WAVES];
             if (loaders && ns == 3 && (long)q.tiles_m * q.tiles_n * (m->in_session ? m->nlanes : 1) <= 256) {
+                tally(m, HD_DBG_X3_32X128_S3_LOADERS + (conv ? 1 : 0));
                 if (conv) hipLaunchKernelGGL((gemm_x3_k<32, 128, 1, 4, true, 3, 4>), grid, dim3(512), 0, st, q);
                 else hipLaunchKernelGGL((gemm_x3_k<32, 128, 1, 4, false, 3, 4>), grid, dim3(512), 0, st, q);
             } else
             if (ns == 3) {
+                tally(m, HD_DBG_X3_32X128_S3 + (conv ? 1 : 0));
                 if (conv) hipLaunchKernelGGL((gemm_x3_k<32, 128, 1, 4, true, 3>), grid, dim3(256), 0, st, q);
                 else hipLaunchKernelGGL((gemm_x3_k<32, 128, 1, 4, false, 3>), grid, dim3(256), 0, st, q);
             } else {
+                tally(m, HD_DBG_X3_32X128_S2 + (conv ? 1 : 0));
                 if (conv) hipLaunchKernelGGL((gemm_x3_k<32, 128, 1, 4, true, 2>), grid, dim3(256), 0, st, q);
                 else hipLaunchKernelGGL((gemm_x3_k<32, 128, 1, 4, false, 2>), grid, dim3(256), 0, st, q);
             }
@@ -1057,26 +1064,35 @@ static void launch_gemm(HdModel* m, GemmP& p, bool conv, bool per_seg, int stats
             const int ns64 = (int)m->opt[HD_OPT_SMALL_STAGES];
             const long ns3_max = m->opt[HD_OPT_SMALL_STAGES3_MAX_GRID];
             if (ns64 == 3 || (ns64 == 0 && (long)q.tiles_m * q.tiles_n <= ns3_max)) {
+                tally(m, HD_DBG_X3_64X128_S3 + (conv ? 1 : 0));
                 if (conv) hipLaunchKernelGGL((gemm_x3_k<64, 128, 2, 2, true, 3>), grid, dim3(256), 0, st, q);
                 else hipLaunchKernelGGL((gemm_x3_k<64, 128, 2, 2, false, 3>), grid, dim3(256), 0, st, q);
-            } else
-            if (conv) hipLaunchKernelGGL((gemm_x3_k<64, 128, 2, 2, true, 2>), grid, dim3(256), 0, st, q);
-            else hipLaunchKernelGGL((gemm_x3_k<64, 128, 2, 2, false, 2>), grid, dim3(256), 0, st, q);
+            } else {
+                tally(m, HD_DBG_X3_64X128_S2 + (conv ? 1 : 0));
+                if (conv) hipLaunchKernelGGL((gemm_x3_k<64, 128, 2, 2, true, 2>), grid, dim3(256), 0, st, q);
+                else hipLaunchKernelGGL((gemm_x3_k<64, 128, 2, 2, false, 2>), grid, dim3(256), 0, st, q);
+            }
         } else if (q.ln_sync) {      // the 128 x 128 tile exists per epilogue set (gemm_x3_k, EPISET): the meeting epilogue has its own registers
+            tally(m, HD_DBG_X3_128X128_LNSYNC + (conv ? 1 : 0));
             if (conv) hipLaunchKernelGGL((gemm_x3_k<128, 128, 2, 2, true, 2, 0, 2>), grid, dim3(256), 0, st, q);
             else hipLaunchKernelGGL((gemm_x3_k<128, 128, 2, 2, false, 2, 0, 2>), grid, dim3(256), 0, st, q);
         } else {
+            tally(m, HD_DBG_X3_128X128_PLAIN + (conv ? 1 : 0));
             if (conv) hipLaunchKernelGGL((gemm_x3_k<128, 128, 2, 2, true, 2, 0, 1>), grid, dim3(256), 0, st, q);
             else hipLaunchKernelGGL((gemm_x3_k<128, 128, 2, 2, false, 2, 0, 1>), grid, dim3(256), 0, st, q);
         }
     } else
     if (big && fast_ok && tiles128 < small_tiles) {
         // few 128-row tiles (narrow outputs of the token encoder): 64-row tiles balance the 256 CUs better
+        tally(m, HD_DBG_F32_64X128);
         launch_gemm_t<64, 128, 2, 2, 16>(p, conv, per_seg, st);
     } else if (big) {
-        if (gemm_bk() == 32 || !fast_ok) launch_gemm_t<128, 128, 2, 2, 32>(p, conv, per_seg, st);
+        const bool bk32 = gemm_bk() == 32 || !fast_ok;
+        tally(m, bk32 ? HD_DBG_F32_128X128_BK32 : HD_DBG_F32_128X128_BK16);
+        if (bk32) launch_gemm_t<128, 128, 2, 2, 32>(p, conv, per_seg, st);
         else launch_gemm_t<128, 128, 2, 2, 16>(p, conv, per_seg, st);
     } else {
+        tally(m, HD_DBG_F32_32X128);
         launch_gemm_t<32, 128, 1, 4, 32>(p, conv, per_seg, st);
     }
     if (!p.part) return;
@@ -1259,6 +1275,7 @@ static void attention_layer(HdModel* m, const Segs& sg, const AttLayerW& w, cons
 #endif
         const int NH = fuse19 ? 1 : 2;
         dim3 fgrid((unsigned)(((sg.B + 7) / 8) * 8 * (m->cfg.nhead / NH)));
+        tally(m, fuse19 ? HD_DBG_QKV_ATTN_19 : HD_DBG_QKV_ATTN_10);
         if (fuse19) hipLaunchKernelGGL((qkv_attn_x3_k<19, 1>), fgrid, dim3(QA_THREADS), lds_request(QaGeom<19, 1>::smem(m->L), QA_THREADS), st, q);
         else hipLaunchKernelGGL((qkv_attn_x3_k<10, 2>), fgrid, dim3(QA_THREADS), lds_request(QaGeom<10, 2>::smem(m->L), QA_THREADS), st, q);
         p = base_gemm(m, sg);
@@ -1289,6 +1306,8 @@ static void attention_layer(HdModel* m, const Segs& sg, const AttLayerW& w, cons
     const bool ax_kernel = ax_ok && ((m->L > 16 * 18 && m->L <= 16 * 19) || (m->L > 16 * 9 && m->L <= 16 * 10));
     if (ax_kernel && (long)grid.x <= m->opt[HD_OPT_ATTN_QSPLIT_MAX_GRID]) grid.y = 2;
     const bool ax_w8 = m->opt[HD_OPT_ATTN_WAVES] == 8;
+    if (grid.y == 2) tally(m, HD_DBG_ATTN_QSPLIT);
+    tally(m, !ax_kernel ? HD_DBG_ATTN_F32 : m->L > 160 ? (ax_w8 ? HD_DBG_ATTN_X3_19_W8 : HD_DBG_ATTN_X3_19_W12) : HD_DBG_ATTN_X3_10);
     if (ax_ok && m->L > 16 * 18 && m->L <= 16 * 19 && !ax_w8)
         hipLaunchKernelGGL((attn_x3_k<19, AX19_THREADS>), grid, dim3(AX19_THREADS), lds_request(AxGeom<19>::SMEM, AX19_THREADS), st, cur(m).ws.QKV, 3 * A, A, m->rope_cos, m->rope_sin, cur(m).ws.O, A, m->cfg.nhead, sg, osp, rsp);
     else if (ax_ok && m->L > 16 * 18 && m->L <= 16 * 19)
@@ -1369,7 +1388,10 @@ static void pruned_tail(HdModel* m, const Segs& sg, const AttBlockW& w) {
     const float2* at_part = p.spart; const int at_pw = p.spw; const long at_rows = p.spart_rows;
     if (att_x3(m, sg)) { p.A = ws.ATX; use_x3(p, w.a2.wqkvx, A / X3_BN); }     // column slice [A, ...) = n tiles from A / 128 on
     launch_gemm(m, p, false, false);
-    if (tail_form(m, B) == TAIL_SLICED) {          // everything behind the K projection in five launches (hd_tail_fused.hip.h)
+    const bool sliced = tail_form(m, B) == TAIL_SLICED;
+    tally(m, sliced ? HD_DBG_TAIL_SLICED : HD_DBG_TAIL_LAUNCHES);
+    tally(m, via_rows ? HD_DBG_VALUE_VIA_ROWS : HD_DBG_VALUE_VIA_PROJECTION);      // (the sliced form exists with via_rows only: tail_form)
+    if (sliced) {          // everything behind the K projection in five launches (hd_tail_fused.hip.h)
         TailP t{};
         t.AT = ws.AT; t.Y = ws.Y; t.D = D; t.QKV = ws.QKV; t.ldq = 3 * A; t.A = A;
         t.at_part = at_part; t.at_pw = at_pw; t.at_rows = at_rows;
@@ -1926,6 +1948,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         }
     }
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipEventRecord(m->lane[l].ev0, m->lane[l].stream));
+    tally(m, HD_DBG_SAMPLE_LANES_1 + m->nlanes - 1);
     // HD_LOOP_GRAPH (or HUDIFF_LOOP_GRAPH=1): the whole [t0, t1) loop of a lane is one graph -- a chain of t1 - t0 child-graph
     // nodes of the captured step (the step counter lives on the device, so every step is the same node) -- kept for the next
     // sample with the same number of steps.  Default: the step graph is launched t1 - t0 times, which measured 2.4 % faster
@@ -1949,6 +1972,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             }
         }
         for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipGraphLaunch(m->lane[l].loop_exec, m->lane[l].stream));
+        tally(m, HD_DBG_LOOP_GRAPH);
     } else if (use_graph) {
         // the lanes are fed alternately; on the device they run concurrently and drift freely (no cross-lane edges)
         for (int t = t0; t < t1; ++t)
@@ -2165,6 +2189,14 @@ extern "C" HdStatus hd_last_run_ms(HdModel* m, float* ms, int32_t* steps) {
 extern "C" HdStatus hd_debug_stop_after(HdModel* m, int32_t stage) {
     if (!m) return fail(HD_ERR_INVALID, "hd_debug_stop_after: null model");
     m->debug_stop_after = stage;   // 1: after the token encoder (+static add), 2+n: before attention block n
+    return HD_OK;
+}
+
+extern "C" HdStatus hd_debug_launch_tally(HdModel* m, int64_t* counts, int32_t n) {
+    if (!m || n < 0 || (n > 0 && !counts)) return fail(HD_ERR_INVALID, "hd_debug_launch_tally: null argument");
+    for (int i = 0; i < n && i < HD_DBG_COUNT; ++i) counts[i] = m->tally[i];
+    for (int i = HD_DBG_COUNT; i < n; ++i) counts[i] = 0;
+    memset(m->tally, 0, sizeof(m->tally));
     return HD_OK;
 }
 

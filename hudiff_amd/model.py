@@ -404,6 +404,13 @@ class _Denoiser:
     def debug_scatter_lnsync(self, on=True):
         L.check(self._lib.hd_debug_scatter_lnsync(self._h, 1 if on else 0))
 
+    def debug_launch_tally(self):
+        """hd_debug_launch_tally: {kernel name: launches issued since the last call} (host-side count, cleared by the call; a launch
+        captured into a graph counts once, so read it as "> 0").  Names: hudiff_amd._lib.DEBUG_KERNELS."""
+        counts = (C.c_int64 * len(L.DEBUG_KERNELS))()
+        L.check(self._lib.hd_debug_launch_tally(self._h, counts, len(L.DEBUG_KERNELS)))
+        return {n: int(counts[i]) for i, n in enumerate(L.DEBUG_KERNELS)}
+
     def debug_stop_after(self, stage):
         L.check(self._lib.hd_debug_stop_after(self._h, int(stage)))
 

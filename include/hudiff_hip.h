@@ -49,7 +49,7 @@ extern "C" {
 
 #define HD_ABI_VERSION 1      /* layout of HdConfig; rounds 4-5 added entry points only (hd_set_precision, hd_precision_report, hd_precision_reset,
                                  hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
-                                 hd_score and the flag HD_RECORD_LOGP */
+                                 hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -253,7 +253,9 @@ HdStatus hd_precision_reset(HdModel* m);
  * route: an explicit hd_set_option wins; an option nobody set takes the environment variable named beside it if that is exported
  * when hd_create runs, else the default.  hd_set_option is legal between calls (HD_ERR_STATE inside a sampling session; options
  * marked [create] only before hd_finalize); it drops the handle's captured graphs.  Values outside [lo, hi] -> HD_ERR_INVALID.
- * None of them changes results beyond the last-ulp reassociation documented in INTEGRATION.md (tile shapes share one K order).     */
+ * None of them changes results beyond the last-ulp reassociation documented in INTEGRATION.md (tile shapes share one K order):
+ * tests/test_gpu_x3.py test_tuning_options_interface (tokens) and tests/test_gpu_variants.py (every selectable kernel, stage by stage,
+ * against a float64 evaluation; hd_debug_launch_tally below witnesses which kernel ran).                                          */
 typedef enum HdOption {
     HD_OPT_LANES = 0,               /* HUDIFF_LANES            2     [1, 4]   lanes (stream + workspace + graph) a sampling batch is split into          */
     HD_OPT_LANE_MIN_ROWS = 1,       /* HUDIFF_LANE_MIN_B       16    [2, ..]  fewest rows of a batch that is split into lanes                           */
@@ -311,6 +313,52 @@ HdStatus hd_debug_read(HdModel* m, const char* name, int32_t B, float* out, int6
  * consecutive slots, so that the cross-XCD path of the meeting (write-through partials, agent-scope loads) is the one that runs;
  * results must be bit-identical to the normal placement and hd_precision_report then says lnsync_cross_xcd = 1. */
 HdStatus hd_debug_scatter_lnsync(HdModel* m, int32_t on);
+/* Launch tally: which kernels the handle's launchers chose since the last call of this function.  Counted on the HOST where the launch
+ * is issued (no device code takes part), so a launch issued under graph capture counts once however often the graph is replayed, and a
+ * handle that reuses a captured graph counts nothing: the witness is "> 0", never an exact number.  Copies min(n, HD_DBG_COUNT) counters
+ * into `counts` (may be NULL with n = 0) and clears all of them.  The split GEMM ids come in pairs: id + 1 is the tap (conv) instantiation. */
+typedef enum HdDebugKernel {
+    HD_DBG_X3_256X256_S2 = 0,         /* gemm_x3_k: 256 x 256 tile, two stages (8 waves)                              */
+    HD_DBG_X3_256X256_S2_CONV = 1,
+    HD_DBG_X3_256X128_S3 = 2,         /*            256 x 128, three stages (8 waves)                                 */
+    HD_DBG_X3_256X128_S3_CONV = 3,
+    HD_DBG_X3_128X128_PLAIN = 4,      /*            128 x 128, plain epilogue set                                     */
+    HD_DBG_X3_128X128_PLAIN_CONV = 5,
+    HD_DBG_X3_128X128_LNSYNC = 6,     /*            128 x 128, ln_sync (meeting) epilogue set                         */
+    HD_DBG_X3_128X128_LNSYNC_CONV = 7,
+    HD_DBG_X3_64X128_S2 = 8,
+    HD_DBG_X3_64X128_S2_CONV = 9,
+    HD_DBG_X3_64X128_S3 = 10,
+    HD_DBG_X3_64X128_S3_CONV = 11,
+    HD_DBG_X3_32X128_S2 = 12,
+    HD_DBG_X3_32X128_S2_CONV = 13,
+    HD_DBG_X3_32X128_S3 = 14,
+    HD_DBG_X3_32X128_S3_CONV = 15,
+    HD_DBG_X3_32X128_S3_LOADERS = 16, /*            32 x 128, three stages, four DMA-issuing waves                    */
+    HD_DBG_X3_32X128_S3_LOADERS_CONV = 17,
+    HD_DBG_F32_128X128_BK16 = 18,     /* gemm_k (fp32 MFMA pipe)                                                      */
+    HD_DBG_F32_128X128_BK32 = 19,
+    HD_DBG_F32_64X128 = 20,
+    HD_DBG_F32_32X128 = 21,
+    HD_DBG_QKV_ATTN_19 = 22,          /* qkv_attn_x3_k<19, 1>: projection fused into the attention kernel             */
+    HD_DBG_QKV_ATTN_10 = 23,          /* qkv_attn_x3_k<10, 2>                                                         */
+    HD_DBG_ATTN_X3_19_W12 = 24,       /* attn_x3_k<19>, 12 waves                                                      */
+    HD_DBG_ATTN_X3_19_W8 = 25,        /* attn_x3_k<19>, 8 waves                                                       */
+    HD_DBG_ATTN_X3_10 = 26,           /* attn_x3_k<10>                                                                */
+    HD_DBG_ATTN_F32 = 27,             /* attn_k (fp32 attention core)                                                 */
+    HD_DBG_ATTN_QSPLIT = 28,          /* an attention core launch whose query tiles are shared by two workgroups      */
+    HD_DBG_TAIL_SLICED = 29,          /* pruned tail: five sliced launches                                            */
+    HD_DBG_TAIL_LAUNCHES = 30,        /* pruned tail: separate launches                                               */
+    HD_DBG_VALUE_VIA_ROWS = 31,       /* pruned tail: value side through the input rows                               */
+    HD_DBG_VALUE_VIA_PROJECTION = 32, /* pruned tail: value side through a V projection of every row                  */
+    HD_DBG_SAMPLE_LANES_1 = 33,       /* hd_sample_run enqueued steps on 1 .. 4 lanes                                 */
+    HD_DBG_SAMPLE_LANES_2 = 34,
+    HD_DBG_SAMPLE_LANES_3 = 35,
+    HD_DBG_SAMPLE_LANES_4 = 36,
+    HD_DBG_LOOP_GRAPH = 37,           /* hd_sample_run launched the whole loop of a lane as one graph                 */
+    HD_DBG_COUNT = 38
+} HdDebugKernel;
+HdStatus hd_debug_launch_tally(HdModel* m, int64_t* counts, int32_t n);
 
 #ifdef __cplusplus
 }

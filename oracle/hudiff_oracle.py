@@ -382,7 +382,9 @@ class OracleNet:
         s = self.sd
         pre = f"self_at.layers.{n}."
         at = x + self._attn(x, pre + "attn_hl.")
+        self._rec(f"att{n}_at1", at)                    # (the same trace keys as hudiff_oracle_torch.TorchOracleNet)
         at = at + self._attn(layer_norm(at, s[pre + "norm_hl1.weight"], s[pre + "norm_hl1.bias"]), pre + "attn_hl_c.")
+        self._rec(f"att{n}_at2", at)
         f = layer_norm(at, s[pre + "norm_hl2.weight"], s[pre + "norm_hl2.bias"])
         f = relu(linear(f, s[pre + "ff_hl.0.weight"], s[pre + "ff_hl.0.bias"]))
         f = linear(f, s[pre + "ff_hl.2.weight"], s[pre + "ff_hl.2.bias"])

@@ -79,6 +79,24 @@ def test_option_table_matches_header():
     assert lib.hd_debug_scatter_lnsync(None, 1) == _lib.HD_ERR_INVALID
 
 
+def test_launch_tally_table_matches_header():
+    """hd_debug_launch_tally: the binding's kernel names are the header's HdDebugKernel enum, in order; every split GEMM id is
+    followed by its tap (conv) twin; the entry point validates its arguments without a device."""
+    from hudiff_amd import _lib
+    text = open(os.path.join(ROOT, "include", "hudiff_hip.h")).read()
+    body = re.search(r"typedef enum HdDebugKernel \{(.*?)\} HdDebugKernel;", text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    enum = [(n, int(v)) for n, v in re.findall(r"(HD_DBG_[A-Z0-9_]+)\s*=\s*(\d+)", body)]
+    assert enum[-1][0] == "HD_DBG_COUNT" and enum[-1][1] == len(enum) - 1
+    assert [v for _, v in enum] == list(range(len(enum)))
+    assert [n[len("HD_DBG_"):].lower() for n, _ in enum[:-1]] == list(_lib.DEBUG_KERNELS)
+    x3 = [n for n in _lib.DEBUG_KERNELS if n.startswith("x3_")]
+    assert len(x3) == 18 and all(x3[i + 1] == x3[i] + "_conv" for i in range(0, len(x3), 2))
+    lib = _lib.load()
+    counts = (C.c_int64 * len(_lib.DEBUG_KERNELS))()
+    assert lib.hd_debug_launch_tally(None, counts, len(counts)) == _lib.HD_ERR_INVALID
+
+
 def test_no_cpu_fallback():
     import hudiff_amd
     from hudiff_amd._lib import HD_ERR_NO_DEVICE, HudiffError

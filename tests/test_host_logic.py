@@ -409,3 +409,41 @@ def test_bench_dump_outputs_writes_float32_tokens_within_the_limit(tmp_path, mon
     got = np.load(tmp_path / "e" / "tokens.npy")
     assert got.shape == (10, 291) and rows.dtype == np.float64 and (np.diff(rows) > 0).all()
     assert np.array_equal(got, tok[rows.astype(np.int64)]) and np.array_equal(rows, np.load(tmp_path / "f" / "tokens_rows.npy"))
+
+
+def test_every_option_and_kernel_choice_has_a_variant_case():
+    """tests/test_gpu_variants.py: every option hd_set_option knows is set by a case there (or named in ELSEWHERE with the test file
+    that sweeps it), every option a case sets exists, and every kernel choice the launch tally can report is witnessed by some
+    case (or named in UNREACHED with the reason).  A new option or kernel id without a case fails here, without a GPU."""
+    import test_gpu_variants as tv
+    from hudiff_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    used = set()
+    for v in tv.FORWARD_VARIANTS:
+        used |= set(v["opts"])
+        assert v["route"] in _lib.PRECISIONS and set(v["kinds"]) <= {"ab", "nb"}
+    for _, route, opts, _, _, _ in tv.SAMPLING_VARIANTS:
+        used |= set(opts)
+        assert route in _lib.PRECISIONS
+    assert used <= set(_lib.OPTIONS), used - set(_lib.OPTIONS)
+    for name in _lib.OPTIONS:
+        if name in used:
+            continue
+        assert name in tv.ELSEWHERE, f"option {name!r} has no case in tests/test_gpu_variants.py and is not listed in ELSEWHERE"
+        assert name in open(os.path.join(root, tv.ELSEWHERE[name])).read(), (name, tv.ELSEWHERE[name])
+    assert not set(tv.ELSEWHERE) & used
+    ids = [f"{k}-{v['route']}-{v['id']}" for v in tv.FORWARD_VARIANTS for k in v["kinds"]]
+    assert len(ids) == len(set(ids)) and len({v[0] for v in tv.SAMPLING_VARIANTS}) == len(tv.SAMPLING_VARIANTS)
+    seen = set()
+    for v in tv.FORWARD_VARIANTS:
+        for kind in v["kinds"]:
+            e, f = set(tv._names(kind, v["expect"])), set(tv._names(kind, v["forbid"]))
+            assert e and not e & f, (v["id"], kind, e & f)
+            seen |= e
+            assert (e | f) <= set(_lib.DEBUG_KERNELS), (v["id"], (e | f) - set(_lib.DEBUG_KERNELS))
+    for name, _, _, _, expect, forbid in tv.SAMPLING_VARIANTS:
+        assert expect and not set(expect) & set(forbid), name
+        assert set(expect) | set(forbid) <= set(_lib.DEBUG_KERNELS), name
+        seen |= set(expect)
+    assert set(tv.X3_ALL) == {n for n in _lib.DEBUG_KERNELS if n.startswith("x3_")}
+    assert set(_lib.DEBUG_KERNELS) - seen == set(tv.UNREACHED), (set(_lib.DEBUG_KERNELS) - seen, tv.UNREACHED)
