@@ -30,6 +30,7 @@ EXPORTS = [
     "hd_set_precision", "hd_precision_report", "hd_precision_reset", "hd_sample_tokens", "hd_debug_fail_next_lnsync",
     "hd_set_option", "hd_get_option", "hd_debug_scatter_lnsync",
     "hd_sample_logp", "hd_score_begin", "hd_score", "hd_debug_launch_tally",
+    "hd_set_guide",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -61,6 +62,11 @@ class HdConfig(C.Structure):
 class HdPrecisionInfo(C.Structure):
     _fields_ = [("precision", C.c_int32), ("split_built", C.c_int32), ("split_in_use", C.c_int32), ("lnsync_in_use", C.c_int32),
                 ("range_fallbacks", C.c_int64), ("lnsync_fallbacks", C.c_int64), ("last_call_repeated", C.c_int32), ("lnsync_cross_xcd", C.c_int32)]
+
+
+class HdGuide(C.Structure):
+    """include/hudiff_hip.h "guided sampling": hd_set_guide copies the arrays; the next begin on the handle consumes the guide."""
+    _fields_ = [("B", C.c_int32), ("temperature", C.c_float), ("allow", C.POINTER(C.c_uint32)), ("bias", C.POINTER(C.c_float))]
 
 
 class HudiffError(RuntimeError):
@@ -121,6 +127,7 @@ def load():
     lib.hd_get_option.argtypes = [vp, C.c_int32, P(C.c_int64)]
     lib.hd_debug_scatter_lnsync.argtypes = [vp, C.c_int32]
     lib.hd_debug_launch_tally.argtypes = [vp, P(C.c_int64), C.c_int32]
+    lib.hd_set_guide.argtypes = [vp, P(HdGuide)]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

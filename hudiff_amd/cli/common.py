@@ -50,6 +50,66 @@ def add_runtime_args(p):
     return p
 
 
+def add_guide_args(p):
+    """Flags of the four samplers that steer the draw (hudiff_amd/guide.py); with none of them given the run is the unguided one."""
+    p.add_argument("--temperature", type=float, default=1.0,
+                   help="temperature of the draw: logits are divided by it; 0 = the greedy decode (no noise)")
+    p.add_argument("--forbid", type=str, default="",
+                   help="residue letters (of ACDEFGHIKLMNPQRSTVWYX) never drawn at any sampled slot, e.g. CM")
+    p.add_argument("--constraints_fpath", type=str, default=None,
+                   help="text file, one 'chain,position,residues' per line: chain H|L, position an IMGT label or *, residues tokenizer "
+                        "letters ('-' included; a leading ! = all but these); lines intersect, # starts a comment")
+    p.add_argument("--bias_fpath", type=str, default=None,
+                   help=".npz whose array 'bias' [max_len, 22] is added to the logits of every input")
+    return p
+
+
+def apply_guide_args(args, kind, jobs, logger=None):
+    """Gives every job the guide the flags of add_guide_args describe and returns the temperature for sample_jobs[_with_retry].  No
+    flag given: the jobs stay unguided.  A constraint of --constraints_fpath on a slot an input does not sample is ignored (their
+    number is logged once); a sampled slot left without an allowed residue is an error."""
+    import numpy as np
+    from ..guide import ALL_TOKENS, Guide, LETTERS, N_DRAW, letters_mask, parse_constraints
+    temperature = float(args.temperature)
+    if not (temperature == 0.0 or 0.01 <= temperature <= 100.0):
+        raise ValueError(f"--temperature {args.temperature}: 0 (greedy) or a value in [0.01, 100]")
+    if not (args.forbid or args.constraints_fpath or args.bias_fpath) or not jobs:
+        return temperature
+    if "-" in args.forbid:
+        raise ValueError("--forbid: '-' (the gap) cannot be forbidden this way; use --constraints_fpath")
+    forbid = letters_mask(args.forbid)
+    L = len(jobs[0].tokens) if np.ndim(jobs[0].tokens) == 1 else np.shape(jobs[0].tokens)[-1]
+    allow = np.full(L, ALL_TOKENS, np.uint32)
+    if args.constraints_fpath:
+        with open(args.constraints_fpath) as f:
+            allow = parse_constraints(f, kind)
+        if allow.shape != (L,):
+            raise ValueError(f"{args.constraints_fpath}: constraints describe {allow.shape[0]} slots, the inputs have {L}")
+    constrained = allow != ALL_TOKENS
+    allow = allow & np.uint32(ALL_TOKENS & ~forbid)
+    bias = None
+    if args.bias_fpath:
+        bias = np.asarray(np.load(args.bias_fpath)["bias"], np.float32)
+        if bias.shape != (L, N_DRAW):
+            raise ValueError(f"{args.bias_fpath}: bias must be [{L}, {N_DRAW}], got {bias.shape}")
+        if not np.isfinite(bias).all():
+            raise ValueError(f"{args.bias_fpath}: bias must be finite (forbid a residue with --forbid / --constraints_fpath)")
+    ignored = 0
+    for job in jobs:
+        loc = np.asarray(job.loc, np.int64)
+        empty = loc[allow[loc] == 0]
+        if len(empty):
+            raise ValueError(f"input {job.name!r}: no residue of {LETTERS} is left at sampled slot {int(empty[0])} "
+                             "(--forbid and --constraints_fpath together exclude everything)")
+        sampled = np.zeros(L, bool)
+        sampled[loc] = True
+        ignored += int((constrained & ~sampled).sum())
+        job.guide = Guide(allow, bias)
+    if logger is not None and args.constraints_fpath:
+        logger.info("Constraints on slots an input does not sample (ignored): {}".format(ignored))
+    return temperature
+
+
 def relaunch_if_asked(args, module, argv):
     """`python -m hudiff_amd.cli.X --gpus N` without a launcher around it: re-execute as N ranks under torch.distributed.run (the
     same shape bench.py uses) and return that job's exit code; None when this process should carry on (single rank, or already a

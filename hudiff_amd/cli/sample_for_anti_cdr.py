@@ -21,7 +21,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_runtime_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
+from .common import add_guide_args, add_runtime_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
 
 
 def build_parser():
@@ -42,6 +42,7 @@ def build_parser():
     p.add_argument("--dropout", choices=["faithful", "off"], default="faithful")
     p.add_argument("--device", type=int, default=None)
     add_runtime_args(p)
+    add_guide_args(p)
     return p
 
 
@@ -102,7 +103,9 @@ def main(argv=None):
         np.random.shuffle(loc)
     job = Job(tokens=tok, region=reg, loc=loc, chain=chain, name=pdb_name)
     passes = max(0, -(-args.sample_number // args.batch_size))                 # every replica looked at counts (:212)
-    result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout)
+    temperature = apply_guide_args(args, "ab", [job], logger)
+    result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout,
+                         **({} if temperature == 1.0 else {"temperature": temperature}))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

@@ -22,7 +22,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_runtime_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
+from .common import add_guide_args, add_runtime_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
 from .nanosample import chain_is_valid
 
 
@@ -45,6 +45,7 @@ def build_parser():
     p.add_argument("--dropout", choices=["faithful", "off"], default="faithful")
     p.add_argument("--device", type=int, default=None)
     add_runtime_args(p)
+    add_guide_args(p)
     return p
 
 
@@ -86,8 +87,10 @@ def main(argv=None):
     if args.sample_order == "shuffle":
         np.random.shuffle(loc)
     passes = max(1, -(-args.sample_number // args.batch_size))
-    result = sample_jobs(model, [Job(tokens=tok, region=reg, loc=loc, name=pdb_name)], args.batch_size, args.seed,
-                         passes=passes, dropout=args.dropout)
+    job = Job(tokens=tok, region=reg, loc=loc, name=pdb_name)
+    temperature = apply_guide_args(args, "nb", [job], logger)
+    result = sample_jobs(model, [job], args.batch_size, args.seed, passes=passes, dropout=args.dropout,
+                         **({} if temperature == 1.0 else {"temperature": temperature}))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

@@ -97,11 +97,16 @@ struct Workspace {
     // [B, Tmax] beside `order` (same capacity, regrown together): log-probability of the token written by row b at step t (recording
     // and scoring sessions), and the token a scoring session forces there
     float* logp = nullptr; int32_t* target = nullptr;
+    // guide of a guided session (hd_set_guide), gathered by step like `target`: allowed-token bits [B, Tmax] (beside `order`, same
+    // capacity) and, when the guide has a bias, [B, Tmax, 22] floats with a capacity of their own
+    uint32_t* gallow = nullptr; float* gbias = nullptr; size_t gbias_cap = 0;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
 
 constexpr int HD_MAX_LANES = 4;
+enum { GUIDE_NONE = 0, GUIDE_ALLOW = 1, GUIDE_ALLOW_BIAS = 2 };
+constexpr uint32_t GUIDE_ALL_TOKENS = (1u << 22) - 1;
 
 // ---- tuning options (include/hudiff_hip.h "tuning options") -----------------------------------------------------------------------
 // One table: id, the environment variable that overrides the DEFAULT of an option nobody set, default, legal range (`set` = the
@@ -211,6 +216,8 @@ struct HdModel {
         int graph_x3 = -1;                           // kernel_set() when the graph was captured (split kernels in use, ln_sync level)
         int graph_mode = -1;                         // draw mode of the captured step (DRAW_SAMPLE / DRAW_RECORD / DRAW_SCORE)
         const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
+        // the guide the captured draw was launched with (GUIDE_*, its temperature -- a kernel argument -- and the buffers it reads)
+        int graph_guide = -1; float graph_temp = 1.f; const uint32_t* graph_gallow = nullptr; const float* graph_gbias = nullptr;
         // the T-step loop as ONE graph: `loop_steps` child-graph nodes of `graph` in a chain (hd_sample_run)
         hipGraph_t loop_graph = nullptr;
         hipGraphExec_t loop_exec = nullptr;
@@ -237,6 +244,13 @@ struct HdModel {
     bool s_has_q = false;
     int s_mode = DRAW_SAMPLE;                        // draw stage of the session: plain, recording (HD_RECORD_LOGP), teacher-forced (hd_score_begin)
     bool logp_ready = false;                         // the lanes' logp buffers hold a finished recording session (hd_sample_logp after the end)
+    // guided sampling (include/hudiff_hip.h "guided sampling"): hd_set_guide leaves a copy here; the next begin takes it (whether it
+    // succeeds or fails) and, if it succeeds, the session keeps it on the device through restarts and guard repeats
+    struct Guide { int32_t B = 0; float temperature = 1.f; bool has_allow = false, has_bias = false; std::vector<uint32_t> allow; std::vector<float> bias; };
+    bool guide_pending = false;
+    Guide guide;
+    int s_guide = GUIDE_NONE;                        // draw of the open session: unguided, allowed bits only, bits and bias
+    float s_temp = 1.f;
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
     int debug_stop_after = 0;     // 0 = run everything (hd_debug_stop_after)
@@ -592,6 +606,31 @@ extern "C" HdStatus hd_set_precision(HdModel* m, int32_t precision) {
     if (precision != HD_PRECISION_DEFAULT && precision != HD_PRECISION_F32_GEMM && precision != HD_PRECISION_F32_ALL && precision != HD_PRECISION_SPLIT)
         return fail(HD_ERR_INVALID, "hd_set_precision: unknown route %d", precision);
     m->precision_req = precision;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "guided sampling": validates and copies; the next begin takes the copy.
+extern "C" HdStatus hd_set_guide(HdModel* m, const HdGuide* g) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_guide: null model");
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_guide: a sampling session is open (the guide belongs to the NEXT begin)");
+    m->guide = HdModel::Guide();
+    m->guide_pending = false;
+    if (!g) return HD_OK;
+    if (g->B < 0) return fail(HD_ERR_INVALID, "hd_set_guide: B = %d", g->B);
+    const float tp = g->temperature;
+    if (!(tp == 0.f || (tp >= 0.01f && tp <= 100.f)))      // (NaN fails every comparison)
+        return fail(HD_ERR_INVALID, "hd_set_guide: temperature %g is neither 0 (greedy) nor in [0.01, 100]", (double)tp);
+    const size_t n = (size_t)g->B * m->L;
+    if (g->bias)
+        for (size_t i = 0; i < n * 22; ++i)
+            if (!std::isfinite(g->bias[i]))
+                return fail(HD_ERR_INVALID, "hd_set_guide: bias[%zu, %zu, %zu] is not finite (forbid a token through `allow`)",
+                            i / 22 / m->L, i / 22 % m->L, i % 22);
+    HdModel::Guide& k = m->guide;
+    k.B = g->B; k.temperature = tp; k.has_allow = g->allow != nullptr; k.has_bias = g->bias != nullptr;
+    if (g->allow) k.allow.assign(g->allow, g->allow + n);
+    if (g->bias) k.bias.assign(g->bias, g->bias + n * 22);
+    m->guide_pending = true;
     return HD_OK;
 }
 
@@ -1741,7 +1780,20 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
     // (the last workgroup of sample_step_k advances the step)
     const float* hm = prune ? ws.Xc : ws.Y;
     const float* qn = m->s_has_q ? m->qnoise : nullptr;
-    if (m->s_mode == DRAW_SAMPLE)
+    if (m->s_guide != GUIDE_NONE) {
+        const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
+        const dim3 grid(sg.B), block(64 * SS_WAVES);
+        const int compact = prune ? 1 : 0;
+        if (m->s_mode == DRAW_SAMPLE)
+            hipLaunchKernelGGL(sample_step_guided_k<DRAW_SAMPLE>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, (float*)nullptr, (const int32_t*)nullptr, g);
+        else if (m->s_mode == DRAW_RECORD)
+            hipLaunchKernelGGL(sample_step_guided_k<DRAW_RECORD>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
+        else
+            hipLaunchKernelGGL(sample_step_guided_k<DRAW_SCORE>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
+    } else if (m->s_mode == DRAW_SAMPLE)
         hipLaunchKernelGGL(sample_step_k, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
                            ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1);
     else if (m->s_mode == DRAW_RECORD)
@@ -1757,7 +1809,7 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
 static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                   uint64_t seed, uint64_t row0, const float* q_noise,
-                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score) {
+                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide) {
     if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -1768,6 +1820,12 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->nlanes = 1; m->cl = 0;
     m->s_mode = score ? DRAW_SCORE : (flags & HD_RECORD_LOGP) ? DRAW_RECORD : DRAW_SAMPLE;
     m->logp_ready = false;
+    m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
+    if (guide) {
+        if (guide->B != B) return fail(HD_ERR_INVALID, "hd_set_guide: the guide describes %d rows, the session has %d", guide->B, B);
+        if (score && guide->temperature == 0.f)
+            return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
+    }
     if (B == 0) { m->in_session = true; return HD_OK; }
     HD_TRY(validate_inputs(m, tokens, region, chain, B));
     for (int b = 0; b < B; ++b) {
@@ -1791,6 +1849,26 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
         for (int b = 0; b < B; ++b)
             for (int t = 0; t < T[b]; ++t) masked[(size_t)b * m->L + order[(size_t)b * Tmax + t]] = 22;
         tokens = masked.data();
+    }
+    // the guide, gathered by step (only visited slots are looked at): gallow [B, Tmax], gbias [B, Tmax, 22]
+    std::vector<uint32_t> gallow;
+    std::vector<float> gbias;
+    if (guide) {
+        const size_t Tm = Tmax > 0 ? Tmax : 1;
+        gallow.assign((size_t)B * Tm, 0u);
+        if (guide->has_bias) gbias.assign((size_t)B * Tm * 22, 0.f);
+        for (int b = 0; b < B; ++b)
+            for (int t = 0; t < T[b]; ++t) {
+                const int s = order[(size_t)b * Tmax + t];
+                const uint32_t a = (guide->has_allow ? guide->allow[(size_t)b * m->L + s] : GUIDE_ALL_TOKENS) & GUIDE_ALL_TOKENS;
+                if (a == 0) return fail(HD_ERR_INVALID, "hd_set_guide: no token is allowed at row %d slot %d (step %d)", b, s, t);
+                if (score && !((a >> target[(size_t)b * Tmax + t]) & 1u))
+                    return fail(HD_ERR_INVALID, "hd_score_begin: token %d at row %d slot %d (step %d) is not allowed by the guide",
+                                target[(size_t)b * Tmax + t], b, s, t);
+                gallow[(size_t)b * Tmax + t] = a;
+                if (guide->has_bias)
+                    memcpy(&gbias[((size_t)b * Tmax + t) * 22], &guide->bias[((size_t)b * m->L + s) * 22], 22 * sizeof(float));
+            }
     }
     const int dm = drop_mode_of(m, flags);
     if (dm == DROP_INJECT && (!enc_masks || !conv_masks)) return fail(HD_ERR_INVALID, "hd_sample_begin: HD_DROPOUT_INJECT needs masks");
@@ -1825,20 +1903,38 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
             if (need > (size_t)ws.capT) {
                 if (ws.order) {                 // regrown: release the old buffers now, not at the next free_ws
                     HIP_TRY(hipStreamSynchronize(ln.stream));
-                    for (void* old : {(void*)ws.order, (void*)ws.logp, (void*)ws.target}) {
+                    for (void* old : {(void*)ws.order, (void*)ws.logp, (void*)ws.target, (void*)ws.gallow}) {
                         for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
                             if (*it == old) { ws.owned.erase(it); break; }
                         hipFree(old);
                     }
-                    ws.order = nullptr; ws.logp = nullptr; ws.target = nullptr; ws.capT = 0;
+                    ws.order = nullptr; ws.logp = nullptr; ws.target = nullptr; ws.gallow = nullptr; ws.capT = 0;
                     // a captured graph holds the old pointers
                     ln.drop_graphs();
                 }
                 HD_TRY(dalloc(ws, &ws.order, need));
                 HD_TRY(dalloc(ws, &ws.logp, need));
                 HD_TRY(dalloc(ws, &ws.target, need));
+                HD_TRY(dalloc(ws, &ws.gallow, need));
                 ws.capT = (int)need;
             }
+            if (guide && guide->has_bias && need * 22 > ws.gbias_cap) {
+                if (ws.gbias) {                 // as above: a captured guided graph holds the old pointer
+                    HIP_TRY(hipStreamSynchronize(ln.stream));
+                    for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
+                        if (*it == (void*)ws.gbias) { ws.owned.erase(it); break; }
+                    hipFree(ws.gbias);
+                    ws.gbias = nullptr; ws.gbias_cap = 0;
+                    ln.drop_graphs();
+                }
+                HD_TRY(dalloc(ws, &ws.gbias, need * 22));
+                ws.gbias_cap = need * 22;
+            }
+        }
+        if (guide && Tmax > 0) {
+            HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
+            if (guide->has_bias)
+                HIP_TRY(hipMemcpyAsync(ws.gbias, gbias.data() + (size_t)off * Tmax * 22, (size_t)Bl * Tmax * 22 * sizeof(float), hipMemcpyHostToDevice, ln.stream));
         }
         if (Tmax > 0) HIP_TRY(hipMemcpyAsync(ws.order, order + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
         HIP_TRY(hipMemcpyAsync(ws.T, T + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
@@ -1870,17 +1966,30 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
     m->cl = 0;
     m->s_row0 = row0;
+    if (guide) { m->s_guide = guide->has_bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW; m->s_temp = guide->temperature; }
     m->in_session = true;
     return HD_OK;
+}
+
+// The guide hd_set_guide left is taken by the begin that follows, whatever becomes of that begin.
+static bool take_guide(HdModel* m, HdModel::Guide* g) {
+    if (!m || !m->guide_pending) return false;
+    *g = std::move(m->guide);
+    m->guide = HdModel::Guide();
+    m->guide_pending = false;
+    return true;
 }
 
 extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                     const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                     uint64_t seed, uint64_t row0, const float* q_noise,
                                     const uint8_t* enc_masks, const uint8_t* conv_masks) {
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false);
-    if (s != HD_OK && m && !m->in_session) {     // a failure half-way through the lane loop must not leave lane state behind
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE;
+    HdModel::Guide g;
+    const bool guided = take_guide(m, &g);
+    const bool was_open = m && m->in_session;
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr);
+    if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
     }
     return s;
 }
@@ -1890,9 +1999,12 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
 extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                    const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                    uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks) {
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true);
-    if (s != HD_OK && m && !m->in_session) {
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE;
+    HdModel::Guide g;
+    const bool guided = take_guide(m, &g);
+    const bool was_open = m && m->in_session;
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr);
+    if (s != HD_OK && m && !was_open) {
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
     }
     return s;
 }
@@ -1933,7 +2045,9 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         const uint32_t gflags = m->sflags & HD_NO_PRUNE;
         if (!ln.graph_exec || ln.graph_B != ln.B || ln.graph_flags != gflags || ln.graph_drop != dm || ln.graph_q != m->s_has_q ||
             ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
-            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode) {
+            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode ||
+            ln.graph_guide != m->s_guide || (m->s_guide != GUIDE_NONE && (ln.graph_temp != m->s_temp || ln.graph_gallow != ln.ws.gallow)) ||
+            (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias)) {
             ln.drop_graphs();
             HIP_TRY(hipStreamSynchronize(ln.stream));
             HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
@@ -1945,6 +2059,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             ln.graph_B = ln.B; ln.graph_flags = gflags; ln.graph_drop = dm; ln.graph_q = m->s_has_q; ln.graph_Tmax = m->sTmax;
             ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
             ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode;
+            ln.graph_guide = m->s_guide; ln.graph_temp = m->s_temp; ln.graph_gallow = ln.ws.gallow; ln.graph_gbias = ln.ws.gbias;
         }
     }
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipEventRecord(m->lane[l].ev0, m->lane[l].stream));

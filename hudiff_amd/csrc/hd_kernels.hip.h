@@ -2480,12 +2480,36 @@ __device__ __forceinline__ void ln_row_regs(const float* __restrict__ x, int D, 
 //                log-probability goes to *logp_out
 // log p_s = (logit_s - max) - log(sum_j exp(logit_j - max)): from the logits, not log(p), so a probability that underflowed in
 // e / esum still has a finite logarithm.
+//
+// GUIDED (compile time; hd_set_guide, include/hudiff_hip.h "guided sampling"): the 22 logits become
+//   g_j = (logit_j + bias_j) / temperature for the tokens j whose bit is set in `allow`, -inf for the others,
+// and everything above (softmax, flag, draw against the SAME noise q, log-probability) is taken from g.  A token that is not allowed
+// enters the argmax with -inf, so an allowed one whose p underflowed to 0 still beats it.  temperature == 0 is the greedy decode:
+// argmax_j (logit_j + bias_j) over the allowed j (lowest index wins), no noise read or generated, and the recorded log-probability is
+// the one under temperature 1.  With all bits set, no bias and temperature 1, g_j == logit_j bit for bit (x / 1.0f == x).
+// The unguided instantiations contain none of this.
+struct GuideP {
+    const uint32_t* allow;   // [B, Tmax] of the lane, gathered by step on the host (as `target`): bit j allows token j
+    const float* bias;       // [B, Tmax, 22] or nullptr
+    float temperature;       // 0 = greedy
+};
 enum { DRAW_SAMPLE = 0, DRAW_RECORD = 1, DRAW_SCORE = 2 };
-template <int NW, int MODE = DRAW_SAMPLE>
+template <int NW, int MODE = DRAW_SAMPLE, bool GUIDED = false>
 __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w, int32_t* __restrict__ tokens, int b, int slot, uint32_t t,
                                            const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
-                                           float* lg, float* __restrict__ logp_out = nullptr, int target = 0) {
+                                           float* lg, float* __restrict__ logp_out = nullptr, int target = 0,
+                                           const uint32_t* __restrict__ g_allow = nullptr, const float* __restrict__ g_bias = nullptr,
+                                           float g_temp = 1.f) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // the guide of this (row, step): asked for before the decoder's dot products, used behind them (wave 0, lane j = token j)
+    [[maybe_unused]] bool allowed = true;
+    [[maybe_unused]] float gb = 0.f;
+    if constexpr (GUIDED) {
+        if (wave == 0) {
+            allowed = lane < 22 && ((*g_allow >> lane) & 1u);
+            if (g_bias && lane < 22) gb = g_bias[lane];
+        }
+    }
     float y[16];
     ln_row_regs(x, D, lane, w, y);
 #pragma unroll
@@ -2501,7 +2525,17 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     }
     __syncthreads();
     if (wave != 0) return;
-    const float mylogit = lane < 22 ? lg[lane] : -INFINITY;
+    float mylogit = lane < 22 ? lg[lane] : -INFINITY;
+    [[maybe_unused]] bool greedy = false;
+    if constexpr (GUIDED) {
+        greedy = g_temp == 0.f;
+        if (allowed) {
+            if (g_bias) mylogit += gb;
+            mylogit = mylogit / (greedy ? 1.f : g_temp);
+        } else {
+            mylogit = -INFINITY;
+        }
+    }
     const float mx = wave_max(mylogit);
     const float e = (lane < 22) ? expf(mylogit - mx) : 0.f;
     const float esum = wave_sum(e);
@@ -2518,7 +2552,9 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     }
     const float p = e / esum;
     float q = 1.f;
-    if (lane < 22) {
+    bool noise = lane < 22;
+    if constexpr (GUIDED) noise = noise && !greedy;
+    if (noise) {
         if (q_noise) {
             q = q_noise[((long)t * q_rows + q_off + b) * 22 + lane];     // [Tmax, rows of the whole batch, 22]
         } else {
@@ -2529,6 +2565,7 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
         }
     }
     float ratio = (lane < 22) ? p / q : -INFINITY;
+    if constexpr (GUIDED) ratio = !allowed ? -INFINITY : greedy ? mylogit : ratio;
     int best = lane;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -2547,12 +2584,13 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
 // one-thread launch per step that advance_step_k was.
 // logp / target: [B, Tmax] of the lane (row b at step t), used by the recording and the teacher-forced kernel below only.
 constexpr int SS_WAVES = 16;
-template <int MODE>
+template <int MODE, bool GUIDED = false>
 __device__ __forceinline__ void sample_step_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
                                                  const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
                                                  const float* __restrict__ q_noise, int q_rows, int q_off,
                                                  RunState* __restrict__ rs, const Segs& sg, int compact, int advance,
-                                                 float* __restrict__ logp, const int32_t* __restrict__ target) {
+                                                 float* __restrict__ logp, const int32_t* __restrict__ target,
+                                                 [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f}) {
     __shared__ float lg[32];
     const int b = blockIdx.x;
     const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2560,7 +2598,12 @@ __device__ __forceinline__ void sample_step_body(const float* __restrict__ Hm, i
         const int slot = order[(long)b * Tmax + t];
         // compact: Hm is [B, D] holding only the visited row of each sequence (pruned last block)
         const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
-        if constexpr (MODE == DRAW_SAMPLE)
+        if constexpr (GUIDED) {
+            const long bt = (long)b * Tmax + t;
+            sample_row<SS_WAVES, MODE, true>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
+                                             MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
+                                             g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature);
+        } else if constexpr (MODE == DRAW_SAMPLE)
             sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
         else
             sample_row<SS_WAVES, MODE>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg, logp + (long)b * Tmax + t,
@@ -2596,6 +2639,19 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_logp_k(const float*
                                                      float* __restrict__ logp, const int32_t* __restrict__ target) {
     static_assert(MODE == DRAW_RECORD || MODE == DRAW_SCORE, "the plain draw is sample_step_k");
     sample_step_body<MODE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target);
+}
+
+// The step of a GUIDED session (hd_set_guide) in any of the three draw modes; logp / target may be nullptr in DRAW_SAMPLE.  Sessions
+// without a guide never launch it.
+template <int MODE>
+__global__ void __launch_bounds__(64 * SS_WAVES) sample_step_guided_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                     int32_t* __restrict__ tokens,
+                                                     const int32_t* __restrict__ order,
+                                                     const int32_t* __restrict__ T, int Tmax,
+                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance,
+                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideP g) {
+    sample_step_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target, g);
 }
 
 // Full decoder for hd_forward: logits[b, l, :] = Linear(LN(h[row(b,l)])) , one wave per (b, l).

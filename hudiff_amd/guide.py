@@ -1,0 +1,150 @@
+"""Guided sampling: per-slot residue constraints, temperature and logit bias (include/hudiff_hip.h "guided sampling").
+
+For row b visiting slot s with raw logits z[0:22] the draw stage of a guided session uses
+
+    g_j   = (z_j + bias[b, s, j]) / temperature    for the tokens j allowed at (b, s), -inf for the others
+    p     = softmax(g);  token = argmax_j p_j / q_j  (q = the noise of the unguided draw);  logp = log p_token
+
+``allow[b, s]`` is a uint32 whose bit j (0..21, the tokenizer's ids: 'ACDEFGHIKLMNPQRSTVWY', 'X' = 20, '-' = 21) allows token j.
+temperature == 0 is the greedy decode: argmax_j (z_j + bias_j) over the allowed j, no noise; its recorded log-probability is the
+token's under the temperature-1 guided distribution.
+
+A ``Guide`` is what ``model.sample(..., guide=)`` / ``model.score(..., guide=)`` and ``sampler.Job.guide`` take; ``guided_log_probs`` is
+the same definition in numpy float64 for host-side users; ``parse_constraints`` reads the text form of the CLIs' ``--constraints_fpath``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import tables as T
+from .tokenizer import Tokenizer
+
+N_DRAW = 22                              # tokens the draw stage ranges over (sample.py:510)
+ALL_TOKENS = (1 << N_DRAW) - 1
+_TK = Tokenizer()
+LETTERS = "".join(_TK.toks[:N_DRAW])     # 'ACDEFGHIKLMNPQRSTVWYX-'
+
+
+def letters_mask(letters: str) -> int:
+    """Bits of the tokens named by ``letters`` (tokenizer letters, '-' included); an unknown letter raises ValueError."""
+    m = 0
+    for c in letters:
+        i = LETTERS.find(c)
+        if i < 0:
+            raise ValueError(f"unknown residue letter {c!r} (known: {LETTERS})")
+        m |= 1 << i
+    return m
+
+
+class Guide:
+    """allow: uint32 [L] or [B, L] (None = everything allowed); bias: float32 [L, 22] or [B, L, 22] (None = none); temperature:
+    0 = greedy, else in [0.01, 100].  The [L] forms describe every row of whatever batch consumes the guide."""
+
+    def __init__(self, allow=None, bias=None, temperature=1.0):
+        self.allow = None if allow is None else np.ascontiguousarray(np.asarray(allow), dtype=np.uint32)
+        self.bias = None if bias is None else np.ascontiguousarray(np.asarray(bias), dtype=np.float32)
+        self.temperature = float(temperature)
+        if self.allow is not None and self.allow.ndim not in (1, 2):
+            raise ValueError(f"allow must be [L] or [B, L], got {self.allow.shape}")
+        if self.bias is not None and (self.bias.ndim not in (2, 3) or self.bias.shape[-1] != N_DRAW):
+            raise ValueError(f"bias must be [L, {N_DRAW}] or [B, L, {N_DRAW}], got {self.bias.shape}")
+
+    def batch(self, B, L):
+        """-> (allow uint32 [B, L] or None, bias float32 [B, L, 22] or None), the [L] forms broadcast to B rows."""
+        allow, bias = self.allow, self.bias
+        if allow is not None:
+            if allow.shape not in ((L,), (B, L)):
+                raise ValueError(f"allow must be [{L}] or [{B}, {L}], got {allow.shape}")
+            allow = np.ascontiguousarray(np.broadcast_to(allow, (B, L)))
+        if bias is not None:
+            if bias.shape not in ((L, N_DRAW), (B, L, N_DRAW)):
+                raise ValueError(f"bias must be [{L}, {N_DRAW}] or [{B}, {L}, {N_DRAW}], got {bias.shape}")
+            bias = np.ascontiguousarray(np.broadcast_to(bias, (B, L, N_DRAW)))
+        return allow, bias
+
+    def take(self, rows):
+        """The guide of the rows ``rows`` of the batch this one describes (step-parallel scoring: an expanded row takes the guide of
+        the row it came from)."""
+        rows = np.asarray(rows)
+        allow = self.allow if self.allow is None or self.allow.ndim == 1 else self.allow[rows]
+        bias = self.bias if self.bias is None or self.bias.ndim == 2 else self.bias[rows]
+        return Guide(allow, bias, self.temperature)
+
+    @staticmethod
+    def stack(guides, L, temperature=1.0):
+        """Per-row guides ([L] forms or None) -> one [B, L] guide; rows without a guide allow everything with zero bias."""
+        allow = np.full((len(guides), L), ALL_TOKENS, np.uint32)
+        bias = np.zeros((len(guides), L, N_DRAW), np.float32) if any(g is not None and g.bias is not None for g in guides) else None
+        for r, g in enumerate(guides):
+            if g is None:
+                continue
+            a, b = g.batch(1, L)
+            if a is not None:
+                allow[r] = a[0]
+            if b is not None:
+                bias[r] = b[0]
+        return Guide(allow, bias, temperature)
+
+
+def guided_log_probs(logits22, allow, bias=None, temperature=1.0):
+    """The definition in numpy float64: logits22 [..., 22], allow [...] (uint32 bits), bias [..., 22] or None -> log p [..., 22],
+    -inf where a token is not allowed.  temperature == 0 (greedy) gives the temperature-1 distribution, the one a greedy session
+    records its log-probabilities under; the greedy token is the argmax of the result."""
+    z = np.asarray(logits22, np.float64)
+    if z.shape[-1] != N_DRAW:
+        raise ValueError(f"logits22 must end in {N_DRAW} tokens, got {z.shape}")
+    if bias is not None:
+        z = z + np.asarray(bias, np.float64)
+    tp = float(temperature)
+    if tp != 0.0:
+        z = z / tp
+    ok = ((np.asarray(allow, np.int64)[..., None] >> np.arange(N_DRAW)) & 1).astype(bool)
+    g = np.where(ok, z, -np.inf)
+    mx = g.max(axis=-1, keepdims=True)
+    with np.errstate(divide="ignore"):
+        return (g - mx) - np.log(np.exp(g - mx).sum(axis=-1, keepdims=True))
+
+
+def parse_constraints(lines, kind):
+    """Text constraints -> allow uint32 [L] (L = 291 for kind 'ab', 152 for 'nb').
+
+    One constraint per line, ``chain,position,residues``: chain 'H' or 'L' ('H' only for nanobodies); position an IMGT label of
+    tables.HEAVY_POSITIONS / LIGHT_POSITIONS or '*' (every position of the chain); residues a string of tokenizer letters ('-'
+    included), a leading '!' meaning "all but these".  Lines intersect; '#' starts a comment; an unknown chain, position or letter
+    is a ValueError that names the line."""
+    if kind not in ("ab", "nb"):
+        raise ValueError(f"kind must be 'ab' or 'nb', got {kind!r}")
+    L = T.AB_LEN if kind == "ab" else T.H_LEN
+    allow = np.full(L, ALL_TOKENS, np.uint32)
+    for no, raw in enumerate(lines, 1):
+        line = raw.split("#", 1)[0].strip()
+        if not line:
+            continue
+
+        def bad(why):
+            return ValueError(f"constraints line {no} ({raw.strip()!r}): {why}")
+        parts = [x.strip() for x in line.split(",")]
+        if len(parts) != 3:
+            raise bad("expected chain,position,residues")
+        chain, pos, res = parts
+        if chain == "H":
+            table, base = T.HEAVY_POSITIONS_dict, 0
+        elif chain == "L" and kind == "ab":
+            table, base = T.LIGHT_POSITIONS_dict, T.H_LEN
+        else:
+            raise bad(f"unknown chain {chain!r} (" + ("'H' or 'L'" if kind == "ab" else "a nanobody has 'H' only") + ")")
+        if pos == "*":
+            slots = np.arange(base, base + len(table))
+        elif pos in table:
+            slots = np.array([base + table[pos]])
+        else:
+            raise bad(f"unknown IMGT position {pos!r} of chain {chain}")
+        negate = res.startswith("!")
+        try:
+            mask = letters_mask(res[1:] if negate else res)
+        except ValueError as e:
+            raise bad(str(e)) from None
+        if negate:
+            mask = ALL_TOKENS & ~mask
+        allow[slots] &= np.uint32(mask)
+    return allow

@@ -254,9 +254,27 @@ class _Denoiser:
         cm = None if conv_masks is None else np.ascontiguousarray(conv_masks, dtype=np.uint8)
         return tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch
 
+    def set_guide(self, guide, B=None):
+        """hd_set_guide: the guide (hudiff_amd.guide.Guide; None clears) of the NEXT sample / sample_begin / score / score_begin on
+        this handle, which consumes it whether it succeeds or fails.  ``B``: rows of that session (needed by the [L] forms; default:
+        the rows of a [B, L] / [B, L, 22] array)."""
+        if guide is None:
+            L.check(self._lib.hd_set_guide(self._h, None))
+            return
+        if B is None:
+            B = guide.allow.shape[0] if guide.allow is not None and guide.allow.ndim == 2 else \
+                guide.bias.shape[0] if guide.bias is not None and guide.bias.ndim == 3 else None
+            if B is None:
+                raise ValueError("set_guide: a guide in the [L] forms needs the number of rows B")
+        allow, bias = guide.batch(int(B), self.max_len)
+        g = L.HdGuide(int(B), float(guide.temperature), L.ptr(allow, C.c_uint32), L.ptr(bias, C.c_float))
+        L.check(self._lib.hd_set_guide(self._h, C.byref(g)))
+
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False):
+               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
+
+        ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
 
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
@@ -264,6 +282,8 @@ class _Denoiser:
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
+        if guide is not None:
+            self.set_guide(guide, B)
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                     self._flags(dropout, graph, prune, lanes, bool(return_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
@@ -285,8 +305,10 @@ class _Denoiser:
         return logp
 
     # -- likelihood of given sequences -------------------------------------------------------------
-    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm):
+    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None):
         logp = np.zeros((B, Tmax), dtype=np.float32)
+        if guide is not None:
+            self.set_guide(guide, B)
         L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
                                    L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8), L.ptr(logp, C.c_float)))
@@ -294,7 +316,7 @@ class _Denoiser:
         return logp
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
-              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2):
+              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -302,7 +324,10 @@ class _Denoiser:
         ``parallel``: the tokens are given, so the T steps of a row do not depend on each other: True expands every (row, step) to a
         row of its own (scoring.expand_steps) and runs them as one-step device batches of at most ``device_batch`` rows; False runs
         the sequential T-step loop (hd_score), which is what dropout needs -- generated masks are keyed by (row, step), which an
-        expanded row does not carry.  None: parallel when ``dropout == "off"``."""
+        expanded row does not carry.  None: parallel when ``dropout == "off"``.
+
+        ``guide``: the values are log-probabilities under the guided distribution (hudiff_amd.guide); a token its slot does not allow,
+        or temperature 0, is an error.  Step-parallel: an expanded row takes the guide of the row it came from."""
         if parallel is None:
             parallel = dropout == "off"
         if parallel and dropout != "off":
@@ -312,10 +337,12 @@ class _Denoiser:
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
         flags = self._flags(dropout, graph, prune, lanes)
         if not parallel:
-            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm)
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide)
         else:
             from . import scoring
             x = scoring.expand_steps(tok, reg, chn, order, T)
+            if guide is not None:
+                guide.batch(B, self.max_len)         # (shape check against the batch as given)
             n = x.tokens.shape[0]
             # hd_score takes its targets from the tokens it is given (and masks the slot itself): hand each row its own target back
             x.tokens[np.arange(n), x.order[:, 0]] = tok[x.rows, x.order[:, 0]]
@@ -325,7 +352,7 @@ class _Denoiser:
                 ch = None if x.chain is None else np.ascontiguousarray(np.concatenate([x.chain[s:e], x.chain[n + s:n + e]]))
                 flat[s:e] = self._score_seq(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
                                             np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, 1, flags,
-                                            seed, 0, None, None)[:, 0]
+                                            seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]))[:, 0]
             logp = x.fold(flat, Tmax)
         if was_torch:
             import torch
@@ -333,10 +360,12 @@ class _Denoiser:
         return logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2):
+                    graph=True, prune=True, lanes=2, guide=None):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
         last_run_ms / sample_logp work on it as on a sampling session."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
+        if guide is not None:
+            self.set_guide(guide, B)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
@@ -344,9 +373,11 @@ class _Denoiser:
         self._session_B, self._session_Tmax = B, Tmax
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False):
+                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
+        if guide is not None:
+            self.set_guide(guide, B)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),

@@ -33,6 +33,7 @@ class Job:
     chain: Optional[tuple] = None        # (heavy id, light id) for antibodies
     name: str = ""
     parent: dict = field(default_factory=dict)
+    guide: Optional[object] = None       # hudiff_amd.guide.Guide of this sequence: allow [L] / bias [L, 22] (its temperature is not used)
 
 
 def _id_runs(gids: np.ndarray, max_rows: int):
@@ -49,7 +50,7 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
-                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False):
+                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -58,7 +59,11 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     its noise as global row ``job_ids[job] * replicas + replica``, whatever else is in the batch.
 
     ``return_logp``: also returns float32 [len(jobs), passes, replicas, Tmax], the log-probability of the token each row drew at
-    each step of each pass under the distribution it was drawn from (0 beyond a row's steps); gathered like the tokens."""
+    each step of each pass under the distribution it was drawn from (0 beyond a row's steps); gathered like the tokens.
+
+    ``temperature`` and the jobs' ``guide`` fields steer the draw (hudiff_amd.guide); with no guide on any job and temperature 1 the
+    calls into the library are exactly the unguided ones."""
+    guided = float(temperature) != 1.0 or any(j.guide is not None for j in jobs)
     L = model.max_len
     n_rows = len(jobs) * replicas
     rank, world, _ = D.env_rank_world()
@@ -84,6 +89,9 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
             order[r, :len(j.loc)] = j.loc
             T[r] = len(j.loc)
         chain = np.array([j.chain[0] for j in jb] + [j.chain[1] for j in jb], np.int32) if is_ab else None
+        if guided:
+            from .guide import Guide
+            more = dict(more, guide=Guide.stack([j.guide for j in jb], L, temperature))
         for p in range(passes):
             tok = model.sample(tok, reg, chain, order, T, seed=seed + 1000003 * p, row0=int(gids[cs]), dropout=dropout,
                                q_noise=None if q_noise is None else np.ascontiguousarray(q_noise[p][:Tmax, gids[cs:ce]]), **more)
@@ -123,7 +131,7 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
-                           logp_records: Optional[list] = None) -> List[List[np.ndarray]]:
+                           logp_records: Optional[list] = None, temperature: float = 1.0) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -141,11 +149,13 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
     sweep = 0
     while active:
         sub = [Job(tokens=jobs[j].tokens if state[j]["tokens"] is None else state[j]["tokens"], region=jobs[j].region,
-                   loc=jobs[j].loc, chain=jobs[j].chain, name=jobs[j].name) for j in active]
+                   loc=jobs[j].loc, chain=jobs[j].chain, name=jobs[j].name, guide=jobs[j].guide) for j in active]
         # noise is keyed by the ORIGINAL job index: a sequence's samples do not depend on which other inputs were
         # accepted earlier (or are in the file at all)
         # (q_noise: injected noise of sweep 0 only, [1, Tmax, len(jobs) * replicas, 22] keyed like the generated noise: parity runs)
         more = {} if logp_records is None else {"return_logp": True}
+        if float(temperature) != 1.0:
+            more["temperature"] = temperature
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:

@@ -36,6 +36,10 @@
  *             site = layer for the token encoder (p = cfg.dropout), 64 + layer for Dual/NanoConv (p = 0.5).
  *             mix32(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16.
  *   global_row = row0 + b, so results do not depend on how rows are sharded over GPUs.
+ *   guided    (hd_set_guide, "guided sampling" below): the softmax is taken over g_j = (logits_j + bias_j) / temperature of the allowed
+ *             tokens j; q is EXACTLY the noise of the unguided draw -- the same Philox counter or the same q_noise entry for all 22
+ *             lanes, allowed or not -- and a token that is not allowed enters the argmax with -inf.  temperature == 0 (greedy) reads
+ *             and generates no noise.
  */
 #ifndef HUDIFF_HIP_H
 #define HUDIFF_HIP_H
@@ -49,7 +53,8 @@ extern "C" {
 
 #define HD_ABI_VERSION 1      /* layout of HdConfig; rounds 4-5 added entry points only (hd_set_precision, hd_precision_report, hd_precision_reset,
                                  hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
-                                 hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally */
+                                 hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
+                                 the struct HdGuide */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -182,7 +187,13 @@ HdStatus hd_sample_tokens(HdModel* m, int32_t* tokens);
  * of the scored slots along the ONE visiting order given (the quantity the network was trained on is its mean over orders).
  * hd_sample_run, hd_sample_restart, hd_sync, hd_sample_end (returns the re-filled tokens = the input), hd_sample_tokens,
  * hd_last_run_ms and hd_sample_logp work on that session as on a sampling one; dropout flags, seed / row0 (generated masks) and
- * injected masks mean what they mean for hd_sample.  hd_score = begin + run(0, Tmax) + end + hd_sample_logp. */
+ * injected masks mean what they mean for hd_sample.  hd_score = begin + run(0, Tmax) + end + hd_sample_logp.
+ *
+ * In a GUIDED session ("guided sampling" below) logp is the log-probability under the guided distribution:
+ *     logp[b, t] = (g_s - max_j g_j) - log(sum_j exp(g_j - max_j g_j)),  j over the allowed tokens,
+ * of the drawn token in a recording session and of the target in a scoring one (a target that is not allowed -> HD_ERR_INVALID at
+ * hd_score_begin; so is temperature == 0).  A greedy session (temperature == 0) records the log-probability of its token under
+ * the temperature-1 guided distribution. */
 HdStatus hd_sample_logp(HdModel* m, float* logp /* [B, Tmax] */);
 HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                         const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
@@ -190,6 +201,39 @@ HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region
 HdStatus hd_score(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                   uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks, float* logp /* [B, Tmax] */);
+
+/* ---- guided sampling ------------------------------------------------------------------------------
+ * A guide steers the draw stage of every visited slot of every row of ONE session, sampling or scoring.  For row b visiting slot s
+ * with raw logits z[0:22]:
+ *     g_j   = (z_j + bias[b, s, j]) / temperature     for the tokens j allowed at (b, s)            (fp32)
+ *     g_j   = -inf                                    for the others
+ *     p     = softmax(g) over the allowed j
+ *     token = argmax_j p_j / q_j                      (lowest index wins; a token that is not allowed enters with -inf, so an allowed
+ *                                                      one whose p underflowed to 0 still beats it)
+ *     logp  = (g_token - max g) - log(sum_j exp(g_j - max g))
+ * allow[b, s] is a uint32 whose bit j (0..21) allows token j; q is exactly the noise of the unguided draw (see "Noise").  With all 22
+ * bits set, no (or zero) bias and temperature == 1, g_j == z_j bit for bit and the session produces the tokens and the recorded
+ * log-probabilities of an unguided one bit for bit.  temperature == 0 is the greedy decode: token = argmax_j (z_j + bias_j) over the
+ * allowed j (lowest index wins), no noise is read or generated, and logp is that token's log-probability under the temperature-1
+ * guided distribution.  HD_ERR_NUMERIC is raised from the guided sum exactly as from the raw one.
+ *
+ * Lifetime: hd_set_guide copies the arrays (nothing of the caller's is retained).  The guide applies to the NEXT hd_sample_begin /
+ * hd_sample / hd_score_begin / hd_score on the handle, and that call consumes it whether it succeeds or fails: the session after it
+ * is unguided unless a guide is set again.  Inside its session the guide stays: hd_sample_restart keeps it, and so do the range guard
+ * and the ln_sync guard when they repeat a call.  hd_forward neither uses nor clears it.  NULL clears a guide not yet consumed.
+ * Inside an open session -> HD_ERR_STATE; a NULL handle -> HD_ERR_INVALID.
+ *
+ * HD_ERR_INVALID at hd_set_guide: a temperature that is not finite, negative, or non-zero outside [0.01, 100]; a bias value that is
+ * not finite (forbid a token through `allow`).  At the begin: B differs from the session's; a VISITED slot (b, order[b, t]), t < T[b],
+ * has no allowed token among bits 0..21; in a scoring session a target that is not allowed at its slot, or temperature == 0.  Slots
+ * that are not visited are never checked and never read. */
+typedef struct HdGuide {
+    int32_t B;              /* rows the arrays describe; must equal B of the session that consumes it */
+    float temperature;      /* 0 = greedy, else in [0.01, 100] */
+    const uint32_t* allow;  /* [B, L] or NULL = everything allowed */
+    const float* bias;      /* [B, L, 22] or NULL */
+} HdGuide;
+HdStatus hd_set_guide(HdModel* m, const HdGuide* g);   /* NULL clears */
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
