@@ -30,7 +30,7 @@ EXPORTS = [
     "hd_set_precision", "hd_precision_report", "hd_precision_reset", "hd_sample_tokens", "hd_debug_fail_next_lnsync",
     "hd_set_option", "hd_get_option", "hd_debug_scatter_lnsync",
     "hd_sample_logp", "hd_score_begin", "hd_score", "hd_debug_launch_tally",
-    "hd_set_guide",
+    "hd_set_guide", "hd_set_slots_per_step",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -128,6 +128,7 @@ def load():
     lib.hd_debug_scatter_lnsync.argtypes = [vp, C.c_int32]
     lib.hd_debug_launch_tally.argtypes = [vp, P(C.c_int64), C.c_int32]
     lib.hd_set_guide.argtypes = [vp, P(HdGuide)]
+    lib.hd_set_slots_per_step.argtypes = [vp, C.c_int32]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

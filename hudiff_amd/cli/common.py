@@ -64,6 +64,35 @@ def add_guide_args(p):
     return p
 
 
+def slots_per_step_arg(v):
+    k = int(v)
+    if not 1 <= k <= 64:
+        import argparse
+        raise argparse.ArgumentTypeError(f"{v}: an integer in [1, 64]")
+    return k
+
+
+def add_block_args(p):
+    """--slots_per_step of the four samplers and the scorer (block decoding, include/hudiff_hip.h); without it, or with 1, the run is
+    the one-slot one."""
+    p.add_argument("--slots_per_step", type=slots_per_step_arg, default=1,
+                   help="block decoding: K in [1, 64] slots of a row's visiting order are drawn per denoiser forward, independently "
+                        "from that forward's conditionals -- ceil(T / K) forwards per row instead of T; 1 = one slot per forward")
+    return p
+
+
+def apply_block_args(args, jobs, logger=None):
+    """-> the keywords for sample_jobs[_with_retry] / score_jobs: {} at K = 1 (the calls are then exactly the one-slot ones)."""
+    k = int(args.slots_per_step)
+    if k == 1:
+        return {}
+    if logger is not None:
+        steps = sorted({len(j.loc) for j in jobs})
+        logger.info("Slots per step: {}; forwards per row: {}".format(
+            k, ", ".join("{} (T = {})".format(-(-t // k), t) for t in steps[:8]) + (" ..." if len(steps) > 8 else "")))
+    return {"slots_per_step": k}
+
+
 def apply_guide_args(args, kind, jobs, logger=None):
     """Gives every job the guide the flags of add_guide_args describe and returns the temperature for sample_jobs[_with_retry].  No
     flag given: the jobs stay unguided.  A constraint of --constraints_fpath on a slot an input does not sample is ignored (their

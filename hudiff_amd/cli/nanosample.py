@@ -20,7 +20,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, noise_in_reference_order, sample_jobs_with_retry, seed_all
-from .common import (add_guide_args, add_runtime_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
+from .common import (add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
                      write_logp_csv)
 
 
@@ -55,6 +55,7 @@ def build_parser():
                         "sample_humanization_result.csv (which stays byte-identical)")
     add_runtime_args(p)
     add_guide_args(p)
+    add_block_args(p)
     return p
 
 
@@ -126,6 +127,7 @@ def main(argv=None):
     temperature = apply_guide_args(args, "nb", jobs, logger)
     if temperature != 1.0:
         more["temperature"] = temperature
+    more.update(apply_block_args(args, jobs, logger))
     written = sample_jobs_with_retry(model, jobs, args.batch_size, args.seed, want=args.sample_number,
                                      tries=args.try_number, accept=lambda row: chain_is_valid(I.untokenize_nanobody(row)),
                                      device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise, **more)

@@ -27,7 +27,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, noise_in_reference_order, sample_jobs, seed_all
-from .common import (add_guide_args, add_runtime_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
+from .common import (add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
                      write_logp_csv)
 
 
@@ -72,6 +72,7 @@ def build_parser():
                         "sample_humanization_result.csv (which stays byte-identical)")
     add_runtime_args(p)
     add_guide_args(p)
+    add_block_args(p)
     return p
 
 
@@ -221,6 +222,7 @@ def main(argv=None):
         temperature = apply_guide_args(args, "ab", jobs, logger)
         if temperature != 1.0:
             more["temperature"] = temperature
+        more.update(apply_block_args(args, jobs, logger))
         result = sample_jobs(model, jobs, args.batch_size, args.seed, passes=passes, device_batch=args.device_batch,
                              dropout=args.dropout, q_noise=q_noise, **more)
         if args.logp_fpath:

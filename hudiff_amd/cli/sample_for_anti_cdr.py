@@ -21,7 +21,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_guide_args, add_runtime_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
+from .common import add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
 
 
 def build_parser():
@@ -43,6 +43,7 @@ def build_parser():
     p.add_argument("--device", type=int, default=None)
     add_runtime_args(p)
     add_guide_args(p)
+    add_block_args(p)
     return p
 
 
@@ -105,7 +106,7 @@ def main(argv=None):
     passes = max(0, -(-args.sample_number // args.batch_size))                 # every replica looked at counts (:212)
     temperature = apply_guide_args(args, "ab", [job], logger)
     result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout,
-                         **({} if temperature == 1.0 else {"temperature": temperature}))
+                         **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

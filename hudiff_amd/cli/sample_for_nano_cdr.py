@@ -22,7 +22,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_guide_args, add_runtime_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
+from .common import add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
 from .nanosample import chain_is_valid
 
 
@@ -46,6 +46,7 @@ def build_parser():
     p.add_argument("--device", type=int, default=None)
     add_runtime_args(p)
     add_guide_args(p)
+    add_block_args(p)
     return p
 
 
@@ -90,7 +91,7 @@ def main(argv=None):
     job = Job(tokens=tok, region=reg, loc=loc, name=pdb_name)
     temperature = apply_guide_args(args, "nb", [job], logger)
     result = sample_jobs(model, [job], args.batch_size, args.seed, passes=passes, dropout=args.dropout,
-                         **({} if temperature == 1.0 else {"temperature": temperature}))
+                         **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

@@ -27,7 +27,7 @@ from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint, nanobo
 from ..model import NanoAntiTFNet, model_selected
 from ..sampler import Job
 from ..scoring import score_jobs
-from .common import add_runtime_args, load_numbered, relaunch_if_asked
+from .common import add_block_args, add_runtime_args, apply_block_args, load_numbered, relaunch_if_asked
 
 MASKS = {"ab": ("finetune", "pretrain"), "nb": ("plain", "inpaint")}
 
@@ -51,6 +51,7 @@ def build_parser():
     p.add_argument("--device_batch", type=int, default=256, help="rows per device launch")
     p.add_argument("--device", type=int, default=None)
     p.add_argument("--out_fpath", type=str, default=None)
+    add_block_args(p)
     add_runtime_args(p)
     return p
 
@@ -135,7 +136,8 @@ def main(argv=None):
     if numbered is not None and len(numbered) != len(rows):
         raise ValueError(f"{args.numbered_fpath}: {len(numbered)} rows for {len(rows)} input rows")
     jobs = build_jobs(rows, args.kind, mask, numbered, args.numbering, pad_region)
-    res = score_jobs(model, jobs, orders=args.orders, seed=args.seed, dropout=args.dropout, device_batch=args.device_batch)
+    res = score_jobs(model, jobs, orders=args.orders, seed=args.seed, dropout=args.dropout, device_batch=args.device_batch,
+                     **apply_block_args(args, jobs))
     if rank != 0 or res is None:
         return None
     out = args.out_fpath or os.path.join(os.path.dirname(os.path.abspath(args.data_fpath)), "score_result.csv")

@@ -215,6 +215,7 @@ struct HdModel {
         int graph_qB = -1, graph_qoff = -1;
         int graph_x3 = -1;                           // kernel_set() when the graph was captured (split kernels in use, ln_sync level)
         int graph_mode = -1;                         // draw mode of the captured step (DRAW_SAMPLE / DRAW_RECORD / DRAW_SCORE)
+        int graph_K = -1;                            // slots per step of the captured step (1: pruned tail + sample_step_k; > 1: full last block + sample_block_k)
         const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
         // the guide the captured draw was launched with (GUIDE_*, its temperature -- a kernel argument -- and the buffers it reads)
         int graph_guide = -1; float graph_temp = 1.f; const uint32_t* graph_gallow = nullptr; const float* graph_gbias = nullptr;
@@ -251,6 +252,10 @@ struct HdModel {
     Guide guide;
     int s_guide = GUIDE_NONE;                        // draw of the open session: unguided, allowed bits only, bits and bias
     float s_temp = 1.f;
+    // block decoding (include/hudiff_hip.h "block decoding"): hd_set_slots_per_step leaves K here; the next begin takes it (whether it
+    // succeeds or fails) and, if it succeeds, the session keeps it through restarts and guard repeats
+    int k_next = 1;
+    int sK = 1;                                      // slots per step of the open session
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
     int debug_stop_after = 0;     // 0 = run everything (hd_debug_stop_after)
@@ -606,6 +611,15 @@ extern "C" HdStatus hd_set_precision(HdModel* m, int32_t precision) {
     if (precision != HD_PRECISION_DEFAULT && precision != HD_PRECISION_F32_GEMM && precision != HD_PRECISION_F32_ALL && precision != HD_PRECISION_SPLIT)
         return fail(HD_ERR_INVALID, "hd_set_precision: unknown route %d", precision);
     m->precision_req = precision;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "block decoding": the next begin takes K.
+extern "C" HdStatus hd_set_slots_per_step(HdModel* m, int32_t k) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: null model");
+    if (k < 1 || k > 64) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: k = %d outside [1, 64]", k);
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slots_per_step: a sampling session is open (the block size belongs to the NEXT begin)");
+    m->k_next = k;
     return HD_OK;
 }
 
@@ -1771,11 +1785,43 @@ extern "C" HdStatus hd_forward(HdModel* m, const int32_t* tokens, const int32_t*
 }
 
 // ---- sampling session ---------------------------------------------------------------------------
+// Draw stage of a block session: K order positions per forward, one workgroup per (row, position) on the full hidden buffer.
+static HdStatus block_draw(HdModel* m, const Segs& sg) {
+    HdModel::Lane& ln = cur(m);
+    Workspace& ws = ln.ws;
+    const float* qn = m->s_has_q ? m->qnoise : nullptr;
+    const dim3 grid(sg.B, m->sK), block(64 * SS_WAVES);
+    if (m->s_guide != GUIDE_NONE) {
+        const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
+        if (m->s_mode == DRAW_SAMPLE)
+            hipLaunchKernelGGL(sample_block_guided_k<DRAW_SAMPLE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, (float*)nullptr, (const int32_t*)nullptr, g);
+        else if (m->s_mode == DRAW_RECORD)
+            hipLaunchKernelGGL(sample_block_guided_k<DRAW_RECORD>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
+        else
+            hipLaunchKernelGGL(sample_block_guided_k<DRAW_SCORE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
+    } else if (m->s_mode == DRAW_SAMPLE)
+        hipLaunchKernelGGL(sample_block_k, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                           qn, m->sB, ln.row_off, ln.rs, sg);
+    else if (m->s_mode == DRAW_RECORD)
+        hipLaunchKernelGGL(sample_block_logp_k<DRAW_RECORD>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                           qn, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target);
+    else
+        hipLaunchKernelGGL(sample_block_logp_k<DRAW_SCORE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                           (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, const uint8_t* cm) {
     HdModel::Lane& ln = cur(m);
-    const bool prune = !(m->sflags & HD_NO_PRUNE);
+    // a block session (K > 1) visits K rows per sequence: the last attention block runs for every row, as with HD_NO_PRUNE
+    const bool prune = !(m->sflags & HD_NO_PRUNE) && m->sK == 1;
     HD_TRY(forward_body(m, sg, dm, em, cm, prune));
     Workspace& ws = ln.ws;
+    if (m->sK > 1) return block_draw(m, sg);
     // the injected Exp(1) noise lives once, for the whole batch, in the model (m->qnoise)
     // (the last workgroup of sample_step_k advances the step)
     const float* hm = prune ? ws.Xc : ws.Y;
@@ -1809,7 +1855,7 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
 static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                   uint64_t seed, uint64_t row0, const float* q_noise,
-                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide) {
+                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide, int K) {
     if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -1821,12 +1867,16 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->s_mode = score ? DRAW_SCORE : (flags & HD_RECORD_LOGP) ? DRAW_RECORD : DRAW_SAMPLE;
     m->logp_ready = false;
     m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
+    m->sK = 1;
+    if (K > 1 && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
+        return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop; a session with "
+                                        "%d slots per step takes generated masks or none", K);
     if (guide) {
         if (guide->B != B) return fail(HD_ERR_INVALID, "hd_set_guide: the guide describes %d rows, the session has %d", guide->B, B);
         if (score && guide->temperature == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
     }
-    if (B == 0) { m->in_session = true; return HD_OK; }
+    if (B == 0) { m->sK = K; m->in_session = true; return HD_OK; }
     HD_TRY(validate_inputs(m, tokens, region, chain, B));
     for (int b = 0; b < B; ++b) {
         if (T[b] < 0 || T[b] > Tmax) return fail(HD_ERR_INVALID, "T[%d] = %d out of [0,%d]", b, T[b], Tmax);
@@ -1834,6 +1884,13 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
             int s = order[(size_t)b * Tmax + t];
             if (s < 0 || s >= m->L) return fail(HD_ERR_INVALID, "order[%d,%d] = %d out of [0,%d)", b, t, s, m->L);
         }
+        // block decoding: the K positions of a group are drawn by K workgroups of one launch -- they must write K different tokens
+        for (int t0 = 0; K > 1 && t0 < T[b]; t0 += K)
+            for (int t = t0; t < t0 + K && t < T[b]; ++t)
+                for (int u = t0; u < t; ++u)
+                    if (order[(size_t)b * Tmax + u] == order[(size_t)b * Tmax + t])
+                        return fail(HD_ERR_INVALID, "order[%d,%d] = order[%d,%d] = %d: a slot is repeated inside one group of %d slots per step",
+                                    b, u, b, t, order[(size_t)b * Tmax + t], K);
     }
     // scoring: the caller's tokens are complete; the slots to score become the targets and are masked in the library's copy
     std::vector<int32_t> masked, target;
@@ -1967,6 +2024,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->cl = 0;
     m->s_row0 = row0;
     if (guide) { m->s_guide = guide->has_bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW; m->s_temp = guide->temperature; }
+    m->sK = K;
     m->in_session = true;
     return HD_OK;
 }
@@ -1980,6 +2038,14 @@ static bool take_guide(HdModel* m, HdModel::Guide* g) {
     return true;
 }
 
+// So is the block size hd_set_slots_per_step left.
+static int take_slots_per_step(HdModel* m) {
+    if (!m) return 1;
+    const int k = m->k_next;
+    m->k_next = 1;
+    return k;
+}
+
 extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                     const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                     uint64_t seed, uint64_t row0, const float* q_noise,
@@ -1987,9 +2053,10 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
     HdModel::Guide g;
     const bool guided = take_guide(m, &g);
     const bool was_open = m && m->in_session;
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr);
+    const int K = take_slots_per_step(m);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K);
     if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
     }
     return s;
 }
@@ -2002,9 +2069,10 @@ extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int3
     HdModel::Guide g;
     const bool guided = take_guide(m, &g);
     const bool was_open = m && m->in_session;
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr);
+    const int K = take_slots_per_step(m);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K);
     if (s != HD_OK && m && !was_open) {
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
     }
     return s;
 }
@@ -2031,7 +2099,12 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
 extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_run: no open session");
     if (t0 < 0 || t1 < t0 || t1 > m->sTmax) return fail(HD_ERR_INVALID, "hd_sample_run: steps [%d,%d) outside [0,%d]", t0, t1, m->sTmax);
+    const int K = m->sK;
+    if (K > 1 && (t0 % K != 0 || (t1 % K != 0 && t1 != m->sTmax)))
+        return fail(HD_ERR_INVALID, "hd_sample_run: steps [%d,%d) of a session with %d slots per step: t0 must be a multiple of %d, t1 a multiple or Tmax = %d",
+                    t0, t1, K, K, m->sTmax);
     if (m->sB == 0 || t1 == t0) return HD_OK;
+    const int nf = (t1 - t0 + K - 1) / K;            // denoiser forwards: one per group of K order positions
     HIP_TRY(hipSetDevice(m->device));
     if (t1 > m->s_steps) m->s_steps = t1;
     const int dm = drop_mode_of(m, m->sflags);
@@ -2045,7 +2118,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         const uint32_t gflags = m->sflags & HD_NO_PRUNE;
         if (!ln.graph_exec || ln.graph_B != ln.B || ln.graph_flags != gflags || ln.graph_drop != dm || ln.graph_q != m->s_has_q ||
             ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
-            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode ||
+            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K ||
             ln.graph_guide != m->s_guide || (m->s_guide != GUIDE_NONE && (ln.graph_temp != m->s_temp || ln.graph_gallow != ln.ws.gallow)) ||
             (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias)) {
             ln.drop_graphs();
@@ -2058,7 +2131,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             HIP_TRY(hipGraphInstantiate(&ln.graph_exec, ln.graph, nullptr, nullptr, 0));
             ln.graph_B = ln.B; ln.graph_flags = gflags; ln.graph_drop = dm; ln.graph_q = m->s_has_q; ln.graph_Tmax = m->sTmax;
             ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
-            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode;
+            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K;
             ln.graph_guide = m->s_guide; ln.graph_temp = m->s_temp; ln.graph_gallow = ln.ws.gallow; ln.graph_gbias = ln.ws.gbias;
         }
     }
@@ -2066,34 +2139,35 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
     tally(m, HD_DBG_SAMPLE_LANES_1 + m->nlanes - 1);
     // HD_LOOP_GRAPH (or HUDIFF_LOOP_GRAPH=1): the whole [t0, t1) loop of a lane is one graph -- a chain of t1 - t0 child-graph
     // nodes of the captured step (the step counter lives on the device, so every step is the same node) -- kept for the next
-    // sample with the same number of steps.  Default: the step graph is launched t1 - t0 times, which measured 2.4 % faster
+    // sample with the same number of steps (a block session: one node, or one launch, per group of K positions).  Default: the step
+    // graph is launched t1 - t0 times, which measured 2.4 % faster
     // (the lanes interleave more freely between step graphs than inside two 20 000-node graphs).
     const bool loop_graph = m->opt[HD_OPT_LOOP_GRAPH] != 0 || (m->sflags & HD_LOOP_GRAPH);
-    if (use_graph && loop_graph && t1 - t0 > 1) {
+    if (use_graph && loop_graph && nf > 1) {
         for (int l = 0; l < m->nlanes; ++l) {
             HdModel::Lane& ln = m->lane[l];
-            if (!ln.loop_exec || ln.loop_steps != t1 - t0) {
+            if (!ln.loop_exec || ln.loop_steps != nf) {
                 if (ln.loop_exec) { hipGraphExecDestroy(ln.loop_exec); ln.loop_exec = nullptr; }
                 if (ln.loop_graph) { hipGraphDestroy(ln.loop_graph); ln.loop_graph = nullptr; }
                 HIP_TRY(hipGraphCreate(&ln.loop_graph, 0));
                 hipGraphNode_t prev = nullptr;
-                for (int t = t0; t < t1; ++t) {
+                for (int f = 0; f < nf; ++f) {
                     hipGraphNode_t node = nullptr;
                     HIP_TRY(hipGraphAddChildGraphNode(&node, ln.loop_graph, prev ? &prev : nullptr, prev ? 1 : 0, ln.graph));
                     prev = node;
                 }
                 HIP_TRY(hipGraphInstantiate(&ln.loop_exec, ln.loop_graph, nullptr, nullptr, 0));
-                ln.loop_steps = t1 - t0;
+                ln.loop_steps = nf;
             }
         }
         for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipGraphLaunch(m->lane[l].loop_exec, m->lane[l].stream));
         tally(m, HD_DBG_LOOP_GRAPH);
     } else if (use_graph) {
         // the lanes are fed alternately; on the device they run concurrently and drift freely (no cross-lane edges)
-        for (int t = t0; t < t1; ++t)
+        for (int f = 0; f < nf; ++f)
             for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipGraphLaunch(m->lane[l].graph_exec, m->lane[l].stream));
     } else {
-        for (int t = t0; t < t1; ++t)
+        for (int t = t0; t < t1; t += K)             // (injected masks, indexed by t, come with K == 1 only)
             for (int l = 0; l < m->nlanes; ++l) {
                 m->cl = l;
                 HdModel::Lane& ln = m->lane[l];
@@ -2242,6 +2316,10 @@ extern "C" HdStatus hd_sample(HdModel* m, int32_t* tokens, const int32_t* region
     HD_TRY(hd_sample_begin(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks));
     int tmax_eff = 0;
     for (int b = 0; b < B; ++b) tmax_eff = T[b] > tmax_eff ? T[b] : tmax_eff;
+    if (m->sK > 1) {                                 // whole groups (or up to Tmax): what hd_sample_run takes in a block session
+        tmax_eff = (tmax_eff + m->sK - 1) / m->sK * m->sK;
+        if (tmax_eff > Tmax) tmax_eff = Tmax;
+    }
     HdStatus s = hd_sample_run(m, 0, tmax_eff);
     if (s != HD_OK) { m->in_session = false; m->cl = 0; return s; }
     return hd_sample_end(m, tokens);

@@ -2654,6 +2654,79 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_guided_k(const floa
     sample_step_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target, g);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Block decoding (hd_set_slots_per_step, K = gridDim.y > 1): ONE forward serves the K order positions t = step + j, j = 0 .. K-1.
+// Workgroup (b, j) does what the one-slot kernels above do for row b at position t -- the same sample_row, so the same arithmetic --
+// on the row of slot order[b, t] in the FULL hidden buffer of this forward (Hm is [rows, D]; there is no compact form).  Noise, guide,
+// target and logp are those of position t.  The host has checked that no row repeats a slot inside one group, so no two workgroups
+// write one token.  The last workgroup of the whole grid to finish stores step + K; every workgroup has read `step` before it
+// increments `done`.
+// ------------------------------------------------------------------------------------------------
+template <int MODE, bool GUIDED = false>
+__device__ __forceinline__ void sample_block_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
+                                                  const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
+                                                  const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                  RunState* __restrict__ rs, const Segs& sg,
+                                                  float* __restrict__ logp, const int32_t* __restrict__ target,
+                                                  [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f}) {
+    __shared__ float lg[32];
+    const int b = blockIdx.x;
+    const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t t = step + blockIdx.y;
+    if ((int)t < T[b]) {                                 // (T[b] <= Tmax: checked by the begin)
+        const long bt = (long)b * Tmax + t;
+        const int slot = order[bt];
+        const float* x = Hm + (long)sg.row(b, slot) * D;
+        if constexpr (GUIDED)
+            sample_row<SS_WAVES, MODE, true>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
+                                             MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
+                                             g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature);
+        else if constexpr (MODE == DRAW_SAMPLE)
+            sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
+        else
+            sample_row<SS_WAVES, MODE>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg, logp + bt,
+                                       MODE == DRAW_SCORE ? target[bt] : 0);
+    } else {
+        __syncthreads();                                 // (as sample_step_body: every wave has read the step before thread 0 goes on)
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&rs->done, 1u) == gridDim.x * gridDim.y - 1) {
+            __hip_atomic_store(&rs->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&rs->step, step + gridDim.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+__global__ void __launch_bounds__(64 * SS_WAVES) sample_block_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                     int32_t* __restrict__ tokens,
+                                                     const int32_t* __restrict__ order,
+                                                     const int32_t* __restrict__ T, int Tmax,
+                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                     RunState* __restrict__ rs, Segs sg) {
+    sample_block_body<DRAW_SAMPLE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, nullptr, nullptr);
+}
+template <int MODE>
+__global__ void __launch_bounds__(64 * SS_WAVES) sample_block_logp_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                     int32_t* __restrict__ tokens,
+                                                     const int32_t* __restrict__ order,
+                                                     const int32_t* __restrict__ T, int Tmax,
+                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                     RunState* __restrict__ rs, Segs sg,
+                                                     float* __restrict__ logp, const int32_t* __restrict__ target) {
+    static_assert(MODE == DRAW_RECORD || MODE == DRAW_SCORE, "the plain draw is sample_block_k");
+    sample_block_body<MODE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target);
+}
+template <int MODE>
+__global__ void __launch_bounds__(64 * SS_WAVES) sample_block_guided_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                     int32_t* __restrict__ tokens,
+                                                     const int32_t* __restrict__ order,
+                                                     const int32_t* __restrict__ T, int Tmax,
+                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
+                                                     RunState* __restrict__ rs, Segs sg,
+                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideP g) {
+    sample_block_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g);
+}
+
 // Full decoder for hd_forward: logits[b, l, :] = Linear(LN(h[row(b,l)])) , one wave per (b, l).
 __global__ void __launch_bounds__(256) decode_all_k(const float* __restrict__ Hm, int D, HeadW w, int n_tokens,
                                                      float* __restrict__ logits, Segs sg) {

@@ -270,11 +270,33 @@ class _Denoiser:
         g = L.HdGuide(int(B), float(guide.temperature), L.ptr(allow, C.c_uint32), L.ptr(bias, C.c_float))
         L.check(self._lib.hd_set_guide(self._h, C.byref(g)))
 
+    def set_slots_per_step(self, k):
+        """hd_set_slots_per_step: the block size K in [1, 64] of the NEXT sample / sample_begin / score / score_begin on this handle,
+        which consumes it whether it succeeds or fails (include/hudiff_hip.h "block decoding")."""
+        L.check(self._lib.hd_set_slots_per_step(self._h, int(k)))
+
+    def _arm(self, guide, B, slots_per_step):
+        """What the next begin consumes: the block size (the library is told only when it is not 1) and the guide."""
+        block = int(slots_per_step) != 1
+        if block:
+            self.set_slots_per_step(slots_per_step)
+        if guide is not None:
+            try:
+                self.set_guide(guide, B)
+            except Exception:
+                if block:
+                    self.set_slots_per_step(1)       # (no begin will follow to consume it)
+                raise
+
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None):
+               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
+
+        ``slots_per_step``: block decoding, for this call only -- K in [1, 64] slots of the visiting order are drawn per denoiser
+        forward, independently from that forward's conditionals: ceil(T / K) forwards instead of T; slots drawn in one forward do not
+        see each other.  Position t keeps the noise and the guide it has at K = 1.  1 (default) = the one-slot loop.
 
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
@@ -282,8 +304,7 @@ class _Denoiser:
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
-        if guide is not None:
-            self.set_guide(guide, B)
+        self._arm(guide, B, slots_per_step)
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                     self._flags(dropout, graph, prune, lanes, bool(return_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
@@ -305,10 +326,9 @@ class _Denoiser:
         return logp
 
     # -- likelihood of given sequences -------------------------------------------------------------
-    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None):
+    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1):
         logp = np.zeros((B, Tmax), dtype=np.float32)
-        if guide is not None:
-            self.set_guide(guide, B)
+        self._arm(guide, B, slots_per_step)
         L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
                                    L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8), L.ptr(logp, C.c_float)))
@@ -316,7 +336,7 @@ class _Denoiser:
         return logp
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
-              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None):
+              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -327,7 +347,12 @@ class _Denoiser:
         expanded row does not carry.  None: parallel when ``dropout == "off"``.
 
         ``guide``: the values are log-probabilities under the guided distribution (hudiff_amd.guide); a token its slot does not allow,
-        or temperature 0, is an error.  Step-parallel: an expanded row takes the guide of the row it came from."""
+        or temperature 0, is an error.  Step-parallel: an expanded row takes the guide of the row it came from.
+
+        ``slots_per_step`` = K > 1: the log-likelihood under the block sampler -- logp[b, t] is conditioned on the tokens with
+        ``order[b, (t // K) * K : T[b]]`` masked (the whole group of t, not only t onwards), which is what a sampling session with
+        the same K recorded.  Step-parallel: one expanded row per (row, group), run in sessions of block size K."""
+        K = int(slots_per_step)
         if parallel is None:
             parallel = dropout == "off"
         if parallel and dropout != "off":
@@ -337,22 +362,25 @@ class _Denoiser:
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
         flags = self._flags(dropout, graph, prune, lanes)
         if not parallel:
-            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide)
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K)
         else:
             from . import scoring
-            x = scoring.expand_steps(tok, reg, chn, order, T)
+            x = scoring.expand_steps(tok, reg, chn, order, T, slots_per_step=K)      # (K outside [1, 64]: ValueError)
             if guide is not None:
                 guide.batch(B, self.max_len)         # (shape check against the batch as given)
             n = x.tokens.shape[0]
-            # hd_score takes its targets from the tokens it is given (and masks the slot itself): hand each row its own target back
-            x.tokens[np.arange(n), x.order[:, 0]] = tok[x.rows, x.order[:, 0]]
-            flat = np.zeros(n, dtype=np.float32)
+            # hd_score takes its targets from the tokens it is given (and masks the slots itself): hand each row the targets of its
+            # group back (one slot at K = 1)
+            live = np.arange(K)[None, :] < x.T[:, None]
+            rr = np.broadcast_to(np.arange(n)[:, None], (n, K))[live]
+            x.tokens[rr, x.order[live]] = tok[x.rows[rr], x.order[live]]
+            flat = np.zeros((n, K), dtype=np.float32)
             for s in range(0, n, int(device_batch)):
                 e = min(n, s + int(device_batch))
                 ch = None if x.chain is None else np.ascontiguousarray(np.concatenate([x.chain[s:e], x.chain[n + s:n + e]]))
                 flat[s:e] = self._score_seq(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
-                                            np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, 1, flags,
-                                            seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]))[:, 0]
+                                            np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, K, flags,
+                                            seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]), K)
             logp = x.fold(flat, Tmax)
         if was_torch:
             import torch
@@ -360,12 +388,11 @@ class _Denoiser:
         return logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2, guide=None):
+                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
         last_run_ms / sample_logp work on it as on a sampling session."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
-        if guide is not None:
-            self.set_guide(guide, B)
+        self._arm(guide, B, slots_per_step)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
@@ -373,11 +400,10 @@ class _Denoiser:
         self._session_B, self._session_Tmax = B, Tmax
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None):
+                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
-        if guide is not None:
-            self.set_guide(guide, B)
+        self._arm(guide, B, slots_per_step)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
@@ -385,6 +411,8 @@ class _Denoiser:
         self._session_B, self._session_Tmax = B, Tmax
 
     def sample_run(self, t0, t1):
+        """hd_sample_run: order positions [t0, t1); in a session with K slots per step t0 is a multiple of K and t1 a multiple of K
+        or Tmax, and ceil((t1 - t0) / K) forwards are enqueued."""
         L.check(self._lib.hd_sample_run(self._h, int(t0), int(t1)))
 
     def sample_restart(self, seed):

@@ -50,7 +50,7 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
-                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0):
+                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -62,7 +62,10 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     each step of each pass under the distribution it was drawn from (0 beyond a row's steps); gathered like the tokens.
 
     ``temperature`` and the jobs' ``guide`` fields steer the draw (hudiff_amd.guide); with no guide on any job and temperature 1 the
-    calls into the library are exactly the unguided ones."""
+    calls into the library are exactly the unguided ones.
+
+    ``slots_per_step`` = K > 1: block decoding (model.sample) -- K slots of a row's order per denoiser forward; at 1 the calls into the
+    library are exactly the one-slot ones."""
     guided = float(temperature) != 1.0 or any(j.guide is not None for j in jobs)
     L = model.max_len
     n_rows = len(jobs) * replicas
@@ -73,6 +76,8 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     out = np.zeros((passes, hi - lo, L), np.int32)
     lp = np.zeros((passes, hi - lo, Tmax), np.float32) if return_logp else None
     more = {"return_logp": True} if return_logp else {}
+    if int(slots_per_step) != 1:
+        more["slots_per_step"] = int(slots_per_step)
     jid = np.arange(len(jobs), dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
     pos = np.arange(lo, hi)                                      # positions in the packed (job-major) row list
     gids = jid[pos // replicas] * replicas + pos % replicas      # the ids the noise is keyed by
@@ -131,7 +136,7 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
-                           logp_records: Optional[list] = None, temperature: float = 1.0) -> List[List[np.ndarray]]:
+                           logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -156,6 +161,8 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
         more = {} if logp_records is None else {"return_logp": True}
         if float(temperature) != 1.0:
             more["temperature"] = temperature
+        if int(slots_per_step) != 1:
+            more["slots_per_step"] = int(slots_per_step)
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:

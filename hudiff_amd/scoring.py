@@ -20,26 +20,45 @@ MASK_TOKEN = 22
 
 @dataclass
 class Expanded:
-    """Rows of ``expand_steps``: row i is (source row ``rows[i]``, step ``steps[i]``)."""
+    """Rows of ``expand_steps``: row i is (source row ``rows[i]``, step ``steps[i]``).  With ``slots_per_step`` = K > 1 row i is the
+    group of K order positions of its source row that starts at ``steps[i]`` (a multiple of K)."""
     tokens: np.ndarray                   # [N, L] int32
     region: np.ndarray                   # [N, L] int32
     chain: Optional[np.ndarray]          # [2N] int32 (heavy ids, then light ids) or None
-    order: np.ndarray                    # [N, 1] int32: the slot the row scores
-    T: np.ndarray                        # [N] int32, all 1
+    order: np.ndarray                    # [N, K] int32: the slot(s) the row scores (0 beyond T)
+    T: np.ndarray                        # [N] int32: slots the row scores (all 1 at K = 1; < K in a row's last group)
     rows: np.ndarray                     # [N] source row b
-    steps: np.ndarray                    # [N] step t of the source row
+    steps: np.ndarray                    # [N] (first) step t of the source row
     B: int                               # source rows
+    slots_per_step: int = 1              # K
 
     def fold(self, flat, Tmax: int) -> np.ndarray:
-        """Flat per-row values [N] -> [B, Tmax] float32, 0 where t >= T[b]."""
+        """Per-row values [N] ([N, K] with K slots per step) -> [B, Tmax] float32, 0 where t >= T[b]: the value of row i at
+        position j < T[i] goes to ``[rows[i], steps[i] + j]``."""
         out = np.zeros((self.B, Tmax), np.float32)
-        out[self.rows, self.steps] = np.asarray(flat, np.float32).reshape(-1)
+        if self.slots_per_step == 1:
+            out[self.rows, self.steps] = np.asarray(flat, np.float32).reshape(-1)
+            return out
+        N, K = self.rows.shape[0], self.slots_per_step
+        flat = np.asarray(flat, np.float32).reshape(N, K)
+        j = np.arange(K)[None, :]
+        live = j < np.asarray(self.T)[:, None]
+        out[np.broadcast_to(self.rows[:, None], (N, K))[live], (self.steps[:, None] + j)[live]] = flat[live]
         return out
 
 
-def expand_steps(tokens, region, chain, order, T) -> Expanded:
+def expand_steps(tokens, region, chain, order, T, slots_per_step: int = 1) -> Expanded:
     """Every (b, t < T[b]) becomes one row: the complete tokens of row b with ``order[b, t:T[b]]`` masked, row b's region and
-    chain ids, order ``[order[b, t]]`` and T = 1.  Rows are b-major, t ascending."""
+    chain ids, order ``[order[b, t]]`` and T = 1.  Rows are b-major, t ascending.
+
+    ``slots_per_step`` = K > 1 (block decoding): every (b, f) with f * K < T[b] becomes one row -- ``order[b, f*K:T[b]]`` masked,
+    order = the group ``order[b, f*K : min(f*K + K, T[b])]`` (0-padded to K), T = its length -- to be scored in sessions of block
+    size K with Tmax = K."""
+    K = int(slots_per_step)
+    if not 1 <= K <= 64:
+        raise ValueError(f"slots_per_step must be in [1, 64], got {slots_per_step}")
+    if K > 1:
+        return _expand_groups(tokens, region, chain, order, T, K)
     tokens = np.asarray(tokens, np.int32)
     region = np.asarray(region, np.int32)
     T = np.asarray(T, np.int64).reshape(-1)
@@ -71,6 +90,36 @@ def expand_steps(tokens, region, chain, order, T) -> Expanded:
                     T=np.ones(N, np.int32), rows=rows, steps=steps, B=B)
 
 
+def _expand_groups(tokens, region, chain, order, T, K: int) -> Expanded:
+    tokens = np.asarray(tokens, np.int32)
+    region = np.asarray(region, np.int32)
+    T = np.asarray(T, np.int64).reshape(-1)
+    B, L = tokens.shape
+    order = np.asarray(order, np.int32)
+    order = order.reshape(B, order.shape[1] if order.ndim == 2 else (order.size // B if B else 0))
+    if T.shape[0] != B or (T < 0).any() or (T > order.shape[1]).any():
+        raise ValueError(f"T must be [{B}] with 0 <= T[b] <= {order.shape[1]}")
+    groups = (T + K - 1) // K
+    rows = np.repeat(np.arange(B), groups)
+    steps = np.concatenate([np.arange(0, t, K) for t in T] + [np.zeros(0, np.int64)]).astype(np.int64)
+    N = rows.shape[0]
+    tok = tokens[rows].copy()
+    grp = np.zeros((N, K), np.int32)
+    Tg = np.zeros(N, np.int32)
+    for i in range(N):
+        b, t0, n = int(rows[i]), int(steps[i]), int(T[rows[i]])
+        tok[i, order[b, t0:n]] = MASK_TOKEN
+        Tg[i] = min(K, n - t0)
+        grp[i, :Tg[i]] = order[b, t0:t0 + Tg[i]]
+    ch = None
+    if chain is not None:
+        chain = np.asarray(chain, np.int32).reshape(-1)
+        if chain.shape[0] != 2 * B:
+            raise ValueError(f"chain must be [{2 * B}] (heavy ids, then light ids)")
+        ch = np.concatenate([chain[:B][rows], chain[B:][rows]]).astype(np.int32)
+    return Expanded(tokens=tok, region=region[rows].copy(), chain=ch, order=grp, T=Tg, rows=rows, steps=steps, B=B, slots_per_step=K)
+
+
 def draw_orders(loc, orders: int, seed: int, job_id: int) -> np.ndarray:
     """``orders`` visiting orders of the slots ``loc`` -> [orders, len(loc)]; a function of (seed, job_id, k) alone, so the orders
     of a job do not depend on what else is scored or on how rows are sharded."""
@@ -82,8 +131,10 @@ def draw_orders(loc, orders: int, seed: int, job_id: int) -> np.ndarray:
 
 
 def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout: str = "off", parallel=None,
-               device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None):
+               device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None, slots_per_step: int = 1):
     """Score every job along ``orders`` random visiting orders of its ``loc``.
+
+    ``slots_per_step`` = K > 1 scores under the block sampler (model.score); at 1 the calls into the library are the one-slot ones.
 
     ``Job.tokens`` are COMPLETE sequences here (sampler.Job; ``loc`` = the slots to score, ``region`` / ``chain`` as for sampling).
     Row (job j, order k) is global row ``job_ids[j] * orders + k`` (dropout masks are keyed by it); rows shard over ranks and are
@@ -104,6 +155,7 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
     for j, job in enumerate(jobs):
         all_order[j, :, :len(job.loc)] = draw_orders(job.loc, orders, seed, int(jid[j]))
     out = np.zeros((hi - lo, Tmax), np.float32)
+    more = {} if int(slots_per_step) == 1 else {"slots_per_step": int(slots_per_step)}
     from .sampler import _id_runs
     pos = np.arange(lo, hi)
     gids = jid[pos // orders] * orders + pos % orders
@@ -116,7 +168,7 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
         T = np.array([len(j.loc) for j in jb], np.int32)
         chain = np.array([j.chain[0] for j in jb] + [j.chain[1] for j in jb], np.int32) if is_ab else None
         out[cs:ce] = model.score(tok, reg, chain, order, T, dropout=dropout, parallel=parallel, device_batch=device_batch,
-                                 seed=seed, row0=int(gids[cs]))
+                                 seed=seed, row0=int(gids[cs]), **more)
     # one gather, as for the tokens: the float32 bits travel as int32
     got = D.gather_rows(out.view(np.int32), n_rows, Tmax, all_ranks)
     if got is None:

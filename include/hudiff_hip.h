@@ -40,6 +40,9 @@
  *             tokens j; q is EXACTLY the noise of the unguided draw -- the same Philox counter or the same q_noise entry for all 22
  *             lanes, allowed or not -- and a token that is not allowed enters the argmax with -inf.  temperature == 0 (greedy) reads
  *             and generates no noise.
+ *   block     (hd_set_slots_per_step, "block decoding" below): everything keyed by `step` in the draw -- the Philox counter word, the
+ *             q_noise entry, the guide, target and logp -- stays keyed by the ORDER POSITION t, whatever K is; generated dropout
+ *             masks of forward f are keyed by step = f * K, the forward's first position.
  */
 #ifndef HUDIFF_HIP_H
 #define HUDIFF_HIP_H
@@ -54,7 +57,7 @@ extern "C" {
 #define HD_ABI_VERSION 1      /* layout of HdConfig; rounds 4-5 added entry points only (hd_set_precision, hd_precision_report, hd_precision_reset,
                                  hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
                                  hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
-                                 the struct HdGuide */
+                                 the struct HdGuide; block decoding added hd_set_slots_per_step */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -235,9 +238,38 @@ typedef struct HdGuide {
 } HdGuide;
 HdStatus hd_set_guide(HdModel* m, const HdGuide* g);   /* NULL clears */
 
+/* ---- block decoding -------------------------------------------------------------------------------
+ * A session has a block size K, its "slots per step" (default 1 = one slot per denoiser forward, the loop of the reference).  With
+ * K > 1, forward number f = 0, 1, ... runs the denoiser ONCE on the current tokens and handles the K order positions t = f * K + j,
+ * j = 0 .. K-1: for every row b with t < T[b] it does what step t of a one-slot session does at slot = order[b, t] -- draws (or, when
+ * scoring, writes the target), writes tokens[b, slot], records logp[b, t] -- but from the hidden row of THIS forward, so the slots of
+ * one group do not see each other.  A row takes ceil(T[b] / K) forwards instead of T[b]; the price is that known approximation.
+ *
+ * Keys: position t meets exactly the noise and the guide it meets at K = 1 (see "Noise": Philox counter word `step` = t,
+ * q_noise[t, row, :], the guide of (b, order[b, t]), target[b, t], logp[b, t]).  Generated dropout masks of forward f are keyed by
+ * step = f * K.  The recorded log-probabilities are therefore the exact log-likelihood of the session's tokens under the block
+ * sampler, and a scoring session with the same K, order and guide reproduces them.  The forward of a block session evaluates the
+ * last attention block for every row (as HD_NO_PRUNE and hd_forward do); K = 1 is the one-slot session: the same launches, the same
+ * bits.
+ *
+ * Lifetime: the block size applies to the NEXT hd_sample_begin / hd_sample / hd_score_begin / hd_score on the handle, and that call
+ * consumes it whether it succeeds or fails: the session after it has K = 1 unless a block size is set again.  Inside its session the
+ * block size stays: hd_sample_restart keeps it, and so do the range guard and the ln_sync guard when they repeat a call.  hd_forward
+ * neither uses nor clears it.  Inside an open session -> HD_ERR_STATE; a NULL handle, or k outside [1, 64] -> HD_ERR_INVALID.
+ *
+ * At the begin, with K > 1 only: a row whose order repeats a slot inside one group order[b, f*K : min(f*K + K, T[b])] ->
+ * HD_ERR_INVALID (two workgroups would write one token; the same order stays legal at K = 1); HD_DROPOUT_INJECT ->
+ * HD_ERR_UNSUPPORTED (injected masks are laid out per step of a one-slot loop; generated dropout and dropout off work).
+ *
+ * hd_sample_run(t0, t1) keeps taking ORDER POSITIONS: t0 must be a multiple of K, t1 a multiple of K or equal to Tmax, anything else
+ * -> HD_ERR_INVALID; it enqueues ceil((t1 - t0) / K) forwards.  hd_last_run_ms keeps reporting t1 - t0 in `steps`: the number of
+ * forwards timed is ceil(steps / K). */
+HdStatus hd_set_slots_per_step(HdModel* m, int32_t k);
+
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
- * hd_last_run_ms returns the elapsed device time of the last completed run (after hd_sync/hd_sample_end). */
+ * hd_last_run_ms returns the elapsed device time of the last completed run (after hd_sync/hd_sample_end); `steps` = t1 - t0 order
+ * positions, which took ceil(steps / K) denoiser forwards in a session with K slots per step ("block decoding"). */
 HdStatus hd_last_run_ms(HdModel* m, float* ms, int32_t* steps);
 /* Algorithmic FLOPs of one forward of one row (SURVEY.md §8d formula). */
 double hd_flops_per_row_forward(const HdConfig* cfg);
