@@ -18,6 +18,8 @@ HD_KIND_ANTIBODY, HD_KIND_NANOBODY = 0, 1
 HD_ACT_RELU, HD_ACT_GELU = 1, 2
 HD_DROPOUT_FAITHFUL, HD_DROPOUT_OFF, HD_DROPOUT_INJECT, HD_NO_GRAPH, HD_NO_PRUNE, HD_ONE_LANE, HD_LOOP_GRAPH = 0, 1, 2, 4, 8, 16, 32
 HD_RECORD_LOGP = 64
+HD_SLOTS_GIVEN, HD_SLOTS_CONFIDENT = 0, 1
+SLOT_POLICIES = {"given": HD_SLOTS_GIVEN, "confident": HD_SLOTS_CONFIDENT}
 HD_PRECISION_DEFAULT, HD_PRECISION_F32_GEMM, HD_PRECISION_F32_ALL, HD_PRECISION_SPLIT = 0, 1, 2, 3
 PRECISIONS = {"default": HD_PRECISION_DEFAULT, "split": HD_PRECISION_SPLIT, "f32_gemm": HD_PRECISION_F32_GEMM, "f32_all": HD_PRECISION_F32_ALL}
 PRECISION_NAMES = {HD_PRECISION_SPLIT: "split", HD_PRECISION_F32_GEMM: "f32_gemm", HD_PRECISION_F32_ALL: "f32_all", HD_PRECISION_DEFAULT: "default"}
@@ -30,7 +32,7 @@ EXPORTS = [
     "hd_set_precision", "hd_precision_report", "hd_precision_reset", "hd_sample_tokens", "hd_debug_fail_next_lnsync",
     "hd_set_option", "hd_get_option", "hd_debug_scatter_lnsync",
     "hd_sample_logp", "hd_score_begin", "hd_score", "hd_debug_launch_tally",
-    "hd_set_guide", "hd_set_slots_per_step",
+    "hd_set_guide", "hd_set_slots_per_step", "hd_set_slot_policy", "hd_sample_order",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -129,6 +131,8 @@ def load():
     lib.hd_debug_launch_tally.argtypes = [vp, P(C.c_int64), C.c_int32]
     lib.hd_set_guide.argtypes = [vp, P(HdGuide)]
     lib.hd_set_slots_per_step.argtypes = [vp, C.c_int32]
+    lib.hd_set_slot_policy.argtypes = [vp, C.c_int32]
+    lib.hd_sample_order.argtypes = [vp, i32p]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

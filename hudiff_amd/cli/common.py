@@ -78,19 +78,30 @@ def add_block_args(p):
     p.add_argument("--slots_per_step", type=slots_per_step_arg, default=1,
                    help="block decoding: K in [1, 64] slots of a row's visiting order are drawn per denoiser forward, independently "
                         "from that forward's conditionals -- ceil(T / K) forwards per row instead of T; 1 = one slot per forward")
+    p.add_argument("--slot_policy", choices=("given", "confident"), default="given",
+                   help="which slots a forward fills: 'given' follows each row's visiting order; 'confident' lets the device pick, in "
+                        "every forward, the --slots_per_step remaining slots whose distribution is most peaked (the order is then only "
+                        "the list of slots to fill, and the tie-break)")
     return p
 
 
 def apply_block_args(args, jobs, logger=None):
-    """-> the keywords for sample_jobs[_with_retry] / score_jobs: {} at K = 1 (the calls are then exactly the one-slot ones)."""
+    """-> the keywords for sample_jobs[_with_retry] / score_jobs: {} at K = 1 in the given order (the calls are then exactly the
+    one-slot ones)."""
     k = int(args.slots_per_step)
+    more = {}
+    if getattr(args, "slot_policy", "given") != "given":
+        more["slot_policy"] = args.slot_policy
+        if logger is not None:
+            logger.info("Slot policy: {}".format(args.slot_policy))
     if k == 1:
-        return {}
+        return more
     if logger is not None:
         steps = sorted({len(j.loc) for j in jobs})
         logger.info("Slots per step: {}; forwards per row: {}".format(
             k, ", ".join("{} (T = {})".format(-(-t // k), t) for t in steps[:8]) + (" ..." if len(steps) > 8 else "")))
-    return {"slots_per_step": k}
+    more["slots_per_step"] = k
+    return more
 
 
 def apply_guide_args(args, kind, jobs, logger=None):

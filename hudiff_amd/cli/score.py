@@ -108,7 +108,10 @@ def write_scores(path, jobs, res):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.slot_policy == "confident" and args.orders > 1:
+        parser.error("--slot_policy confident takes --orders 1: the visiting order is the model's own (only ties ever see the list)")
     rc = relaunch_if_asked(args, "hudiff_amd.cli.score", argv)
     if rc is not None:
         return rc

@@ -100,6 +100,10 @@ struct Workspace {
     // guide of a guided session (hd_set_guide), gathered by step like `target`: allowed-token bits [B, Tmax] (beside `order`, same
     // capacity) and, when the guide has a bias, [B, Tmax, 22] floats with a capacity of their own
     uint32_t* gallow = nullptr; float* gbias = nullptr; size_t gbias_cap = 0;
+    // slot policy HD_SLOTS_CONFIDENT (hd_set_slot_policy): the keys slot_conf_k writes [B, Tmax], and the caller's candidate list with
+    // what is keyed by its positions as the begin uploaded them -- slot_select_k permutes order / target / gallow / gbias in place and
+    // hd_sample_restart puts them back from here.  Same capacities (capT, gbias_cap), regrown together with their originals.
+    float* conf = nullptr; int32_t *order0 = nullptr, *target0 = nullptr; uint32_t* gallow0 = nullptr; float* gbias0 = nullptr;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -215,6 +219,7 @@ struct HdModel {
         int graph_qB = -1, graph_qoff = -1;
         int graph_x3 = -1;                           // kernel_set() when the graph was captured (split kernels in use, ln_sync level)
         int graph_mode = -1;                         // draw mode of the captured step (DRAW_SAMPLE / DRAW_RECORD / DRAW_SCORE)
+        int graph_policy = -1;                       // slot policy of the captured step (HD_SLOTS_CONFIDENT: slot_conf_k + slot_select_k in front of the block draw)
         int graph_K = -1;                            // slots per step of the captured step (1: pruned tail + sample_step_k; > 1: full last block + sample_block_k)
         const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
         // the guide the captured draw was launched with (GUIDE_*, its temperature -- a kernel argument -- and the buffers it reads)
@@ -256,6 +261,10 @@ struct HdModel {
     // succeeds or fails) and, if it succeeds, the session keeps it through restarts and guard repeats
     int k_next = 1;
     int sK = 1;                                      // slots per step of the open session
+    // slot policy (include/hudiff_hip.h "slot policy"): hd_set_slot_policy leaves it here; the next begin takes it like the block size
+    int policy_next = HD_SLOTS_GIVEN;
+    int s_policy = HD_SLOTS_GIVEN;                   // slot policy of the open session
+    bool order_ready = false;                        // the lanes' order buffers hold an ended session's order (hd_sample_order after the end)
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
     int debug_stop_after = 0;     // 0 = run everything (hd_debug_stop_after)
@@ -620,6 +629,15 @@ extern "C" HdStatus hd_set_slots_per_step(HdModel* m, int32_t k) {
     if (k < 1 || k > 64) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: k = %d outside [1, 64]", k);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slots_per_step: a sampling session is open (the block size belongs to the NEXT begin)");
     m->k_next = k;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "slot policy": the next begin takes it.
+extern "C" HdStatus hd_set_slot_policy(HdModel* m, int32_t policy) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_slot_policy: null model");
+    if (policy != HD_SLOTS_GIVEN && policy != HD_SLOTS_CONFIDENT) return fail(HD_ERR_INVALID, "hd_set_slot_policy: unknown policy %d", policy);
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slot_policy: a sampling session is open (the policy belongs to the NEXT begin)");
+    m->policy_next = policy;
     return HD_OK;
 }
 
@@ -1743,6 +1761,7 @@ extern "C" HdStatus hd_forward(HdModel* m, const int32_t* tokens, const int32_t*
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_forward: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_forward: a sampling session is open (hd_sample_end it first)");
     m->logp_ready = false;                           // (lane 0's workspace may be regrown below)
+    m->order_ready = false;
     if (B < 0) return fail(HD_ERR_INVALID, "hd_forward: B = %d", B);
     if (B == 0) return HD_OK;
     HIP_TRY(hipSetDevice(m->device));
@@ -1815,13 +1834,44 @@ static HdStatus block_draw(HdModel* m, const Segs& sg) {
     return HD_OK;
 }
 
+// Selection stage of a confident session (HD_SLOTS_CONFIDENT): keys of every remaining position from this forward's hidden rows, then the
+// K best of each row move to the front of its order -- with what is keyed by their positions -- for block_draw to fill.
+static HdStatus slot_choose(HdModel* m, const Segs& sg) {
+    HdModel::Lane& ln = cur(m);
+    Workspace& ws = ln.ws;
+    static_assert(SEL_THREADS >= 304, "slot_select_k: one thread per remaining position of a row (max_len <= 304, hd_create)");
+    const int npos = m->sTmax < m->L ? m->sTmax : m->L;        // (a list without repeats has T[b] <= L)
+    if (npos <= 0) return HD_OK;
+    const dim3 cgrid((npos + SC_WAVES - 1) / SC_WAVES, sg.B), cblock(64 * SC_WAVES);
+    const size_t lds = (size_t)SC_HALF * m->D * sizeof(float);
+    int32_t* tg = m->s_mode == DRAW_SCORE ? ws.target : nullptr;
+    if (m->s_guide != GUIDE_NONE) {
+        const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
+        hipLaunchKernelGGL(slot_conf_k<true>, cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf, g);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(slot_select_k<true>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, tg, ws.T, m->sTmax, m->sK, ln.rs, ws.conf,
+                           ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : (float*)nullptr);
+    } else {
+        hipLaunchKernelGGL(slot_conf_k<false>, cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf,
+                           GuideP{nullptr, nullptr, 1.f});
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(slot_select_k<false>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, tg, ws.T, m->sTmax, m->sK, ln.rs, ws.conf,
+                           (uint32_t*)nullptr, (float*)nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, const uint8_t* cm) {
     HdModel::Lane& ln = cur(m);
-    // a block session (K > 1) visits K rows per sequence: the last attention block runs for every row, as with HD_NO_PRUNE
-    const bool prune = !(m->sflags & HD_NO_PRUNE) && m->sK == 1;
+    // a block session (K > 1) visits K rows per sequence: the last attention block runs for every row, as with HD_NO_PRUNE; so does a
+    // confident session at any K, whose selection needs the hidden row of every remaining slot
+    const bool confident = m->s_policy == HD_SLOTS_CONFIDENT;
+    const bool prune = !(m->sflags & HD_NO_PRUNE) && m->sK == 1 && !confident;
     HD_TRY(forward_body(m, sg, dm, em, cm, prune));
     Workspace& ws = ln.ws;
-    if (m->sK > 1) return block_draw(m, sg);
+    if (confident) HD_TRY(slot_choose(m, sg));
+    if (m->sK > 1 || confident) return block_draw(m, sg);       // (K = 1: gridDim.y == 1, position `step`)
     // the injected Exp(1) noise lives once, for the whole batch, in the model (m->qnoise)
     // (the last workgroup of sample_step_k advances the step)
     const float* hm = prune ? ws.Xc : ws.Y;
@@ -1855,7 +1905,8 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
 static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                   uint64_t seed, uint64_t row0, const float* q_noise,
-                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide, int K) {
+                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide, int K,
+                                  int policy) {
     if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -1866,8 +1917,14 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->nlanes = 1; m->cl = 0;
     m->s_mode = score ? DRAW_SCORE : (flags & HD_RECORD_LOGP) ? DRAW_RECORD : DRAW_SAMPLE;
     m->logp_ready = false;
+    m->order_ready = false;
     m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
     m->sK = 1;
+    m->s_policy = HD_SLOTS_GIVEN;
+    const bool confident = policy == HD_SLOTS_CONFIDENT;
+    if (confident && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
+        return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop in the given order; a "
+                                        "confident session takes generated masks or none");
     if (K > 1 && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
         return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop; a session with "
                                         "%d slots per step takes generated masks or none", K);
@@ -1876,7 +1933,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
         if (score && guide->temperature == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
     }
-    if (B == 0) { m->sK = K; m->in_session = true; return HD_OK; }
+    if (B == 0) { m->sK = K; m->s_policy = policy; m->in_session = true; return HD_OK; }
     HD_TRY(validate_inputs(m, tokens, region, chain, B));
     for (int b = 0; b < B; ++b) {
         if (T[b] < 0 || T[b] > Tmax) return fail(HD_ERR_INVALID, "T[%d] = %d out of [0,%d]", b, T[b], Tmax);
@@ -1891,6 +1948,20 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
                     if (order[(size_t)b * Tmax + u] == order[(size_t)b * Tmax + t])
                         return fail(HD_ERR_INVALID, "order[%d,%d] = order[%d,%d] = %d: a slot is repeated inside one group of %d slots per step",
                                     b, u, b, t, order[(size_t)b * Tmax + t], K);
+    }
+    // slot policy: the candidate list of a confident session is a set -- any of its slots may meet any other in one group
+    if (confident) {
+        std::vector<int> seen((size_t)m->L);
+        for (int b = 0; b < B; ++b) {
+            std::fill(seen.begin(), seen.end(), -1);
+            for (int t = 0; t < T[b]; ++t) {
+                const int s = order[(size_t)b * Tmax + t];
+                if (seen[s] >= 0)
+                    return fail(HD_ERR_INVALID, "order[%d,%d] = order[%d,%d] = %d: the candidate list of a confident session repeats a slot",
+                                b, seen[s], b, t, s);
+                seen[s] = t;
+            }
+        }
     }
     // scoring: the caller's tokens are complete; the slots to score become the targets and are masked in the library's copy
     std::vector<int32_t> masked, target;
@@ -1960,12 +2031,14 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
             if (need > (size_t)ws.capT) {
                 if (ws.order) {                 // regrown: release the old buffers now, not at the next free_ws
                     HIP_TRY(hipStreamSynchronize(ln.stream));
-                    for (void* old : {(void*)ws.order, (void*)ws.logp, (void*)ws.target, (void*)ws.gallow}) {
+                    for (void* old : {(void*)ws.order, (void*)ws.logp, (void*)ws.target, (void*)ws.gallow, (void*)ws.conf, (void*)ws.order0,
+                                      (void*)ws.target0, (void*)ws.gallow0}) {
                         for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
                             if (*it == old) { ws.owned.erase(it); break; }
                         hipFree(old);
                     }
                     ws.order = nullptr; ws.logp = nullptr; ws.target = nullptr; ws.gallow = nullptr; ws.capT = 0;
+                    ws.conf = nullptr; ws.order0 = nullptr; ws.target0 = nullptr; ws.gallow0 = nullptr;
                     // a captured graph holds the old pointers
                     ln.drop_graphs();
                 }
@@ -1973,18 +2046,25 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
                 HD_TRY(dalloc(ws, &ws.logp, need));
                 HD_TRY(dalloc(ws, &ws.target, need));
                 HD_TRY(dalloc(ws, &ws.gallow, need));
+                HD_TRY(dalloc(ws, &ws.conf, need));
+                HD_TRY(dalloc(ws, &ws.order0, need));
+                HD_TRY(dalloc(ws, &ws.target0, need));
+                HD_TRY(dalloc(ws, &ws.gallow0, need));
                 ws.capT = (int)need;
             }
             if (guide && guide->has_bias && need * 22 > ws.gbias_cap) {
                 if (ws.gbias) {                 // as above: a captured guided graph holds the old pointer
                     HIP_TRY(hipStreamSynchronize(ln.stream));
-                    for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
-                        if (*it == (void*)ws.gbias) { ws.owned.erase(it); break; }
-                    hipFree(ws.gbias);
-                    ws.gbias = nullptr; ws.gbias_cap = 0;
+                    for (void* old : {(void*)ws.gbias, (void*)ws.gbias0}) {
+                        for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
+                            if (*it == old) { ws.owned.erase(it); break; }
+                        hipFree(old);
+                    }
+                    ws.gbias = nullptr; ws.gbias0 = nullptr; ws.gbias_cap = 0;
                     ln.drop_graphs();
                 }
                 HD_TRY(dalloc(ws, &ws.gbias, need * 22));
+                HD_TRY(dalloc(ws, &ws.gbias0, need * 22));
                 ws.gbias_cap = need * 22;
             }
         }
@@ -1998,6 +2078,13 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
         if (m->s_mode != DRAW_SAMPLE && Tmax > 0) {
             HIP_TRY(hipMemsetAsync(ws.logp, 0, (size_t)Bl * Tmax * sizeof(float), ln.stream));
             if (score) HIP_TRY(hipMemcpyAsync(ws.target, target.data() + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+        }
+        if (confident && Tmax > 0) {                 // what slot_select_k permutes, as uploaded: hd_sample_restart starts from the caller's list again
+            const size_t nT = (size_t)Bl * Tmax;
+            HIP_TRY(hipMemcpyAsync(ws.order0, ws.order, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (score) HIP_TRY(hipMemcpyAsync(ws.target0, ws.target, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (guide) HIP_TRY(hipMemcpyAsync(ws.gallow0, ws.gallow, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (guide && guide->has_bias) HIP_TRY(hipMemcpyAsync(ws.gbias0, ws.gbias, nT * 22 * sizeof(float), hipMemcpyDeviceToDevice, ln.stream));
         }
         if (l == 0 && q_noise && Tmax > 0) {
             const size_t n = (size_t)Tmax * B * 22;
@@ -2025,6 +2112,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->s_row0 = row0;
     if (guide) { m->s_guide = guide->has_bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW; m->s_temp = guide->temperature; }
     m->sK = K;
+    m->s_policy = policy;
     m->in_session = true;
     return HD_OK;
 }
@@ -2046,6 +2134,14 @@ static int take_slots_per_step(HdModel* m) {
     return k;
 }
 
+// And the slot policy hd_set_slot_policy left.
+static int take_slot_policy(HdModel* m) {
+    if (!m) return HD_SLOTS_GIVEN;
+    const int p = m->policy_next;
+    m->policy_next = HD_SLOTS_GIVEN;
+    return p;
+}
+
 extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                     const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                     uint64_t seed, uint64_t row0, const float* q_noise,
@@ -2054,9 +2150,11 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
     const bool guided = take_guide(m, &g);
     const bool was_open = m && m->in_session;
     const int K = take_slots_per_step(m);
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K);
+    const int policy = take_slot_policy(m);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K, policy);
     if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
+        m->s_policy = HD_SLOTS_GIVEN;
     }
     return s;
 }
@@ -2070,9 +2168,11 @@ extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int3
     const bool guided = take_guide(m, &g);
     const bool was_open = m && m->in_session;
     const int K = take_slots_per_step(m);
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K);
+    const int policy = take_slot_policy(m);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K, policy);
     if (s != HD_OK && m && !was_open) {
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
+        m->s_policy = HD_SLOTS_GIVEN;
     }
     return s;
 }
@@ -2090,6 +2190,13 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (m->s_mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
+        if (m->s_policy == HD_SLOTS_CONFIDENT && m->sTmax > 0) {      // back to the caller's candidate list
+            const size_t nT = (size_t)ln.B * m->sTmax;
+            HIP_TRY(hipMemcpyAsync(ln.ws.order, ln.ws.order0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (m->s_mode == DRAW_SCORE) HIP_TRY(hipMemcpyAsync(ln.ws.target, ln.ws.target0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (m->s_guide != GUIDE_NONE) HIP_TRY(hipMemcpyAsync(ln.ws.gallow, ln.ws.gallow0, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (m->s_guide == GUIDE_ALLOW_BIAS) HIP_TRY(hipMemcpyAsync(ln.ws.gbias, ln.ws.gbias0, nT * 22 * sizeof(float), hipMemcpyDeviceToDevice, ln.stream));
+        }
         HD_TRY(set_run_state(m, seed, m->s_row0 + (uint64_t)ln.row_off, 0));
     }
     m->cl = 0;
@@ -2118,7 +2225,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         const uint32_t gflags = m->sflags & HD_NO_PRUNE;
         if (!ln.graph_exec || ln.graph_B != ln.B || ln.graph_flags != gflags || ln.graph_drop != dm || ln.graph_q != m->s_has_q ||
             ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
-            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K ||
+            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K || ln.graph_policy != m->s_policy ||
             ln.graph_guide != m->s_guide || (m->s_guide != GUIDE_NONE && (ln.graph_temp != m->s_temp || ln.graph_gallow != ln.ws.gallow)) ||
             (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias)) {
             ln.drop_graphs();
@@ -2131,7 +2238,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             HIP_TRY(hipGraphInstantiate(&ln.graph_exec, ln.graph, nullptr, nullptr, 0));
             ln.graph_B = ln.B; ln.graph_flags = gflags; ln.graph_drop = dm; ln.graph_q = m->s_has_q; ln.graph_Tmax = m->sTmax;
             ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
-            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K;
+            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K; ln.graph_policy = m->s_policy;
             ln.graph_guide = m->s_guide; ln.graph_temp = m->s_temp; ln.graph_gallow = ln.ws.gallow; ln.graph_gbias = ln.ws.gbias;
         }
     }
@@ -2235,7 +2342,7 @@ static HdStatus sample_end_impl(HdModel* m, int32_t* tokens, bool* numeric) {
 
 extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_end: no open session");
-    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s_mode != DRAW_SAMPLE; return HD_OK; }
+    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s_mode != DRAW_SAMPLE; m->order_ready = true; return HD_OK; }
     if (!tokens) { m->in_session = false; return fail(HD_ERR_INVALID, "hd_sample_end: null tokens"); }
     bool numeric = false;
     const HdStatus s = sample_end_impl(m, tokens, &numeric);
@@ -2244,6 +2351,7 @@ extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     m->cl = 0;
     if (s != HD_OK) return s;
     m->logp_ready = m->s_mode != DRAW_SAMPLE;        // hd_sample_logp stays legal until the next begin / hd_forward
+    m->order_ready = true;                           // and so does hd_sample_order
     if (numeric)
         return fail(HD_ERR_NUMERIC, "hd_sample: non-finite logits (NaN / inf) at some denoiser step -- weights or inputs out of range; "
                                     "the reference's torch.multinomial raises at this point");
@@ -2340,6 +2448,27 @@ extern "C" HdStatus hd_sample_logp(HdModel* m, float* logp) {
         else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
         if (m->s_dirty) return fail(HD_ERR_STATE, "hd_sample_logp: a guard of the split-precision kernels fired during these steps; their values "
                                                    "are invalid (hd_sample_end repeats the sample)");
+    } else {
+        for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+    }
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "slot policy": the order the session has taken so far (a given-order session: the order it was given).
+extern "C" HdStatus hd_sample_order(HdModel* m, int32_t* order) {
+    if (!m || (!m->in_session && !m->order_ready)) return fail(HD_ERR_STATE, "hd_sample_order: no session (open, or ended and not yet replaced)");
+    if (m->sB == 0 || m->sTmax == 0) return HD_OK;
+    if (!order) return fail(HD_ERR_INVALID, "hd_sample_order: null order");
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(order + (size_t)ln.row_off * m->sTmax, ln.ws.order, (size_t)ln.B * m->sTmax * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+    }
+    if (m->in_session) {
+        if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
+        else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+        if (m->s_dirty) return fail(HD_ERR_STATE, "hd_sample_order: a guard of the split-precision kernels fired during these steps; their order "
+                                                   "is invalid (hd_sample_end repeats the sample)");
     } else {
         for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
     }

@@ -2727,6 +2727,133 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_block_guided_k(const flo
     sample_block_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Slot policy HD_SLOTS_CONFIDENT (hd_set_slot_policy, include/hudiff_hip.h "slot policy"): two launches in front of the block draw
+// pick, per row, WHICH of its remaining order positions this forward fills.  Neither advances rs->step; the launch boundaries order
+// keys -> permutation -> draw.  Sessions without the policy launch neither.
+//
+// slot_conf_k: one wave per (row b, order position i); a workgroup takes SC_WAVES consecutive positions of one row and leaves at once
+// when none of them is in [min(step, T[b]), T[b]).  Each wave normalises the hidden row of slot order[b, i] (ln_row_regs, as the draw
+// does) and takes the 22 decoder dot products against weights staged in LDS -- 11 decoder rows at a time (11 * D floats <= 44 KiB), so
+// the 22 * D weights are read from L2 once per workgroup, not once per position.  Lane j < 22 then holds g_j (the guide applied as
+// sample_row applies it) and the key is c = sum_j exp(g_j - max_j g_j) = 1 / max_j p_j in fp32: butterfly reductions in a fixed order,
+// no atomics, so a session repeats bit for bit.  conf [B, Tmax] of the lane.
+// ------------------------------------------------------------------------------------------------
+constexpr int SC_WAVES = 16;
+constexpr int SC_HALF = 11;                              // decoder rows staged per pass (2 passes = the 22 tokens of the draw)
+template <bool GUIDED>
+__global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                   const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
+                                                   const RunState* __restrict__ rs, Segs sg, float* __restrict__ conf,
+                                                   [[maybe_unused]] GuideP g) {
+    extern __shared__ float sc_w[];                      // [SC_HALF, D]
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int Tb = T[b];                                 // (0 <= T[b] <= Tmax: checked by the begin)
+    const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int n = step < (uint32_t)Tb ? (int)step : Tb;
+    const int i0 = blockIdx.x * SC_WAVES;
+    if (i0 >= Tb || i0 + SC_WAVES <= n) return;          // (the whole workgroup: nothing below is reached by a part of it)
+    const int i = i0 + wave;
+    const bool live = i >= n && i < Tb;
+    const long bi = (long)b * Tmax + i;
+    float y[16];
+    if (live) ln_row_regs(Hm + (long)sg.row(b, order[bi]) * D, D, lane, w, y);
+    float z = -INFINITY;                                 // lane j < 22: logit of token j
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        if (half) __syncthreads();                       // every wave is done with the first 11 rows
+        for (int e = threadIdx.x; e < SC_HALF * D; e += 64 * SC_WAVES) sc_w[e] = w.w[(long)half * SC_HALF * D + e];
+        __syncthreads();
+        if (live) {
+            for (int jj = 0; jj < SC_HALF; ++jj) {
+                float a = 0.f;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) { int c = lane + 64 * k; if (c < D) a += y[k] * sc_w[jj * D + c]; }
+                a = wave_sum(a) + w.b[half * SC_HALF + jj];
+                if (lane == half * SC_HALF + jj) z = a;
+            }
+        }
+    }
+    if (!live) return;
+    if constexpr (GUIDED) {
+        const bool allowed = lane < 22 && ((g.allow[bi] >> lane) & 1u);
+        if (allowed) {
+            if (g.bias) z += g.bias[bi * 22 + lane];
+            z = z / (g.temperature == 0.f ? 1.f : g.temperature);
+        } else {
+            z = -INFINITY;
+        }
+    }
+    const float mx = wave_max(z);
+    const float c = wave_sum(lane < 22 ? expf(z - mx) : 0.f);
+    if (lane == 0) conf[bi] = c;
+}
+
+// slot_select_k: one workgroup per row, one thread per remaining position (a confident session's list has no repeated slot, so there
+// are at most L <= 304 of them).  Keys go to LDS, a key that is not a finite positive number becomes +inf (behind every finite one),
+// every thread counts the (c, i) pairs smaller than its own -- its rank -- and the min(K, remaining) smallest move to the front in
+// rank order; the others follow in their previous relative order.  Each thread holds its own entry (slot, target, guide) in registers
+// across the barriers, so every read of the row is done before the first write.
+constexpr int SEL_THREADS = 320;
+template <bool GUIDED>
+__global__ void __launch_bounds__(SEL_THREADS) slot_select_k(int32_t* __restrict__ order, int32_t* __restrict__ target,
+                                                   const int32_t* __restrict__ T, int Tmax, int K,
+                                                   const RunState* __restrict__ rs, const float* __restrict__ conf,
+                                                   [[maybe_unused]] uint32_t* __restrict__ gallow, [[maybe_unused]] float* __restrict__ gbias) {
+    __shared__ float key[SEL_THREADS];
+    __shared__ int front[SEL_THREADS];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Tb = T[b];
+    const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int n = step < (uint32_t)Tb ? (int)step : Tb;
+    const int N = Tb - n;
+    if (N <= 0 || N > SEL_THREADS) return;               // (N <= L <= 304: the begin rejects a list that repeats a slot)
+    const int k = K < N ? K : N;
+    const bool live = tid < N;
+    const long p0 = (long)b * Tmax + n;
+    float c = INFINITY;
+    int slot = 0, tg = 0;
+    [[maybe_unused]] uint32_t ga = 0;
+    [[maybe_unused]] float gb[22];
+    if (live) {
+        c = conf[p0 + tid];
+        if (!(c > 0.f && c < INFINITY)) c = INFINITY;
+        slot = order[p0 + tid];
+        if (target) tg = target[p0 + tid];
+        if constexpr (GUIDED) {
+            ga = gallow[p0 + tid];
+            if (gbias) {
+#pragma unroll
+                for (int j = 0; j < 22; ++j) gb[j] = gbias[(p0 + tid) * 22 + j];
+            }
+        }
+    }
+    key[tid] = c;
+    __syncthreads();
+    int r = 0;
+    if (live)
+        for (int u = 0; u < N; ++u) { const float cu = key[u]; r += (cu < c || (cu == c && u < tid)) ? 1 : 0; }
+    front[tid] = (live && r < k) ? 1 : 0;
+    __syncthreads();
+    if (!live) return;
+    int dst = r;
+    if (r >= k) {
+        int ahead = 0;                                   // chosen positions in front of this one
+        for (int u = 0; u < tid; ++u) ahead += front[u];
+        dst = k + (tid - ahead);
+    }
+    order[p0 + dst] = slot;
+    if (target) target[p0 + dst] = tg;
+    if constexpr (GUIDED) {
+        gallow[p0 + dst] = ga;
+        if (gbias) {
+#pragma unroll
+            for (int j = 0; j < 22; ++j) gbias[(p0 + dst) * 22 + j] = gb[j];
+        }
+    }
+}
+
 // Full decoder for hd_forward: logits[b, l, :] = Linear(LN(h[row(b,l)])) , one wave per (b, l).
 __global__ void __launch_bounds__(256) decode_all_k(const float* __restrict__ Hm, int D, HeadW w, int n_tokens,
                                                      float* __restrict__ logits, Segs sg) {

@@ -105,6 +105,29 @@ def guided_log_probs(logits22, allow, bias=None, temperature=1.0):
         return (g - mx) - np.log(np.exp(g - mx).sum(axis=-1, keepdims=True))
 
 
+def confidence_keys(logits, allow=None, bias=None, temperature=1.0):
+    """The key of slot_policy="confident" (include/hudiff_hip.h "slot policy") in numpy float64: logits [..., >= 22] (the first 22
+    tokens are the draw's), allow [...] uint32 bits or None (everything allowed), bias [..., 22] or None -> log c [...], with
+        c = sum_j exp(g_j - max_j g_j) = 1 / max_j p_j,   g_j = (z_j + bias_j) / temperature over the allowed tokens, -inf elsewhere
+    (divisor 1 at temperature 0, as the draw).  Smaller is more confident.  A slot whose c is not a finite positive number -- a NaN
+    or +inf logit, nothing allowed -- gets +inf: it ranks behind every finite key."""
+    z = np.asarray(logits, np.float64)[..., :N_DRAW]
+    if z.shape[-1] != N_DRAW:
+        raise ValueError(f"logits must end in at least {N_DRAW} tokens, got {z.shape}")
+    if bias is not None:
+        z = z + np.asarray(bias, np.float64)
+    tp = float(temperature)
+    if tp != 0.0:
+        z = z / tp
+    if allow is not None:
+        ok = ((np.asarray(allow, np.int64)[..., None] >> np.arange(N_DRAW)) & 1).astype(bool)
+        z = np.where(ok, z, -np.inf)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        c = np.exp(z - z.max(axis=-1, keepdims=True)).sum(axis=-1)
+        good = np.isfinite(c) & (c > 0)
+        return np.where(good, np.log(np.where(good, c, 1.0)), np.inf)
+
+
 def parse_constraints(lines, kind):
     """Text constraints -> allow uint32 [L] (L = 291 for kind 'ab', 152 for 'nb').
 

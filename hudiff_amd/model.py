@@ -275,21 +275,51 @@ class _Denoiser:
         which consumes it whether it succeeds or fails (include/hudiff_hip.h "block decoding")."""
         L.check(self._lib.hd_set_slots_per_step(self._h, int(k)))
 
-    def _arm(self, guide, B, slots_per_step):
-        """What the next begin consumes: the block size (the library is told only when it is not 1) and the guide."""
+    def set_slot_policy(self, policy):
+        """hd_set_slot_policy: "given" (follow the order as written) or "confident" (the device picks, forward by forward, the
+        remaining slots it is surest about; include/hudiff_hip.h "slot policy") for the NEXT sample / sample_begin / score /
+        score_begin on this handle, which consumes it whether it succeeds or fails."""
+        L.check(self._lib.hd_set_slot_policy(self._h, self._policy_id(policy)))
+
+    @staticmethod
+    def _policy_id(policy):
+        if isinstance(policy, str):
+            if policy not in L.SLOT_POLICIES:
+                raise ValueError(f"slot_policy must be one of {sorted(L.SLOT_POLICIES)}, got {policy!r}")
+            return L.SLOT_POLICIES[policy]
+        return int(policy)
+
+    def sample_order(self, B=None, Tmax=None):
+        """hd_sample_order: the order int32 [B, Tmax] of the open session as it stands, or of the last session: positions below
+        min(steps run, T[b]) are the slots row b visited, in visiting order (a given-order session returns the order it was given)."""
+        B = self._session_B if B is None else B
+        Tmax = self._session_Tmax if Tmax is None else Tmax
+        order = np.zeros((B, Tmax), dtype=np.int32)
+        L.check(self._lib.hd_sample_order(self._h, L.ptr(order, C.c_int32)))
+        return order
+
+    def _arm(self, guide, B, slots_per_step, slot_policy="given"):
+        """What the next begin consumes: the block size (the library is told only when it is not 1), the slot policy (told only when
+        it is not "given") and the guide."""
+        policy = self._policy_id(slot_policy)
         block = int(slots_per_step) != 1
         if block:
             self.set_slots_per_step(slots_per_step)
-        if guide is not None:
-            try:
+        try:
+            if policy != L.HD_SLOTS_GIVEN:
+                L.check(self._lib.hd_set_slot_policy(self._h, policy))
+            if guide is not None:
                 self.set_guide(guide, B)
-            except Exception:
-                if block:
-                    self.set_slots_per_step(1)       # (no begin will follow to consume it)
-                raise
+        except Exception:
+            if block:
+                self.set_slots_per_step(1)           # (no begin will follow to consume it)
+            if policy != L.HD_SLOTS_GIVEN:
+                self._lib.hd_set_slot_policy(self._h, L.HD_SLOTS_GIVEN)
+            raise
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1):
+               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1,
+               slot_policy="given"):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
@@ -298,13 +328,18 @@ class _Denoiser:
         forward, independently from that forward's conditionals: ceil(T / K) forwards instead of T; slots drawn in one forward do not
         see each other.  Position t keeps the noise and the guide it has at K = 1.  1 (default) = the one-slot loop.
 
+        ``slot_policy``: "given" (default) visits ``order`` as written; "confident" treats ``order[b, :T[b]]`` as the row's candidate
+        list (no slot twice) and lets the device fill, in every forward, the K remaining slots whose distribution is most peaked in
+        that forward (include/hudiff_hip.h "slot policy"); ``sample_order()`` afterwards returns the order taken.
+
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
         are the same with and without it."""
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
-        self._arm(guide, B, slots_per_step)
+        self._arm(guide, B, slots_per_step, slot_policy)
+        self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                     self._flags(dropout, graph, prune, lanes, bool(return_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
@@ -326,9 +361,10 @@ class _Denoiser:
         return logp
 
     # -- likelihood of given sequences -------------------------------------------------------------
-    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1):
+    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given"):
         logp = np.zeros((B, Tmax), dtype=np.float32)
-        self._arm(guide, B, slots_per_step)
+        self._arm(guide, B, slots_per_step, slot_policy)
+        self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
                                    L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8), L.ptr(logp, C.c_float)))
@@ -336,7 +372,7 @@ class _Denoiser:
         return logp
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
-              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1):
+              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given"):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -351,10 +387,18 @@ class _Denoiser:
 
         ``slots_per_step`` = K > 1: the log-likelihood under the block sampler -- logp[b, t] is conditioned on the tokens with
         ``order[b, (t // K) * K : T[b]]`` masked (the whole group of t, not only t onwards), which is what a sampling session with
-        the same K recorded.  Step-parallel: one expanded row per (row, group), run in sessions of block size K."""
+        the same K recorded.  Step-parallel: one expanded row per (row, group), run in sessions of block size K.
+
+        ``slot_policy`` = "confident": teacher-forced under the confident sampler -- ``order[b, :T[b]]`` is the candidate list, the
+        library picks the visiting order (``sample_order()`` afterwards) and logp[b, t] belongs to position t of THAT order.  The slot
+        of step t depends on the steps before it, so there is no step-parallel form: ``parallel=True`` raises, None runs the loop."""
         K = int(slots_per_step)
+        confident = self._policy_id(slot_policy) != L.HD_SLOTS_GIVEN
+        if confident and parallel:
+            raise ValueError("step-parallel scoring cannot follow slot_policy='confident': the slot of step t depends on the steps "
+                             "before it; use parallel=False (or None)")
         if parallel is None:
-            parallel = dropout == "off"
+            parallel = dropout == "off" and not confident
         if parallel and dropout != "off":
             raise ValueError("step-parallel scoring needs dropout='off': dropout masks are keyed by (row, step), "
                              "which an expanded row does not carry; use parallel=False")
@@ -362,7 +406,7 @@ class _Denoiser:
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
         flags = self._flags(dropout, graph, prune, lanes)
         if not parallel:
-            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K)
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy)
         else:
             from . import scoring
             x = scoring.expand_steps(tok, reg, chn, order, T, slots_per_step=K)      # (K outside [1, 64]: ValueError)
@@ -388,11 +432,11 @@ class _Denoiser:
         return logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1):
+                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given"):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
         last_run_ms / sample_logp work on it as on a sampling session."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step)
+        self._arm(guide, B, slots_per_step, slot_policy)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
@@ -400,10 +444,11 @@ class _Denoiser:
         self._session_B, self._session_Tmax = B, Tmax
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
-                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1):
+                     enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1,
+                     slot_policy="given"):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step)
+        self._arm(guide, B, slots_per_step, slot_policy)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),

@@ -29,7 +29,7 @@ class Job:
     """One sequence to humanize: masked tokens, region ids, chain ids (antibody) and its visiting order."""
     tokens: np.ndarray                   # [L], or [replicas, L] when replicas continue from different states
     region: np.ndarray
-    loc: np.ndarray                      # already shuffled (or not) by the caller
+    loc: np.ndarray                      # already shuffled (or not) by the caller; the candidate list (and tie-break) under slot_policy="confident"
     chain: Optional[tuple] = None        # (heavy id, light id) for antibodies
     name: str = ""
     parent: dict = field(default_factory=dict)
@@ -50,7 +50,8 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
-                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1):
+                job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1,
+                slot_policy: str = "given", return_order: bool = False):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -65,7 +66,15 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     calls into the library are exactly the unguided ones.
 
     ``slots_per_step`` = K > 1: block decoding (model.sample) -- K slots of a row's order per denoiser forward; at 1 the calls into the
-    library are exactly the one-slot ones."""
+    library are exactly the one-slot ones.
+
+    ``slot_policy`` = "confident": every row's ``loc`` is its candidate list and the device picks, forward by forward, the K slots
+    it is surest about (model.sample); with "given" nothing is passed on and the calls into the library are exactly today's.
+
+    ``return_order``: also returns (last) int32 [len(jobs), passes, replicas, Tmax], the order each row took (model.sample_order;
+    under "given" the order it was handed), gathered like the log-probabilities."""
+    if slot_policy not in ("given", "confident"):
+        raise ValueError(f"slot_policy must be 'given' or 'confident', got {slot_policy!r}")
     guided = float(temperature) != 1.0 or any(j.guide is not None for j in jobs)
     L = model.max_len
     n_rows = len(jobs) * replicas
@@ -78,6 +87,9 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     more = {"return_logp": True} if return_logp else {}
     if int(slots_per_step) != 1:
         more["slots_per_step"] = int(slots_per_step)
+    if slot_policy != "given":
+        more["slot_policy"] = slot_policy
+    od = np.zeros((passes, hi - lo, Tmax), np.int32) if return_order else None
     jid = np.arange(len(jobs), dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
     pos = np.arange(lo, hi)                                      # positions in the packed (job-major) row list
     gids = jid[pos // replicas] * replicas + pos % replicas      # the ids the noise is keyed by
@@ -103,16 +115,23 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
             if return_logp:
                 tok, lp[p, s - lo:e - lo] = tok
             out[p, s - lo:e - lo] = tok
+            if return_order:
+                od[p, s - lo:e - lo] = model.sample_order(len(jb), Tmax)
     gathered = [D.gather_rows(out[p], n_rows, L, all_ranks) for p in range(passes)]
     # (the float32 bits of the log-probabilities travel as int32 through the same gather)
     gathered_lp = [D.gather_rows(lp[p].view(np.int32), n_rows, Tmax, all_ranks) for p in range(passes)] if return_logp else None
+    gathered_od = [D.gather_rows(od[p], n_rows, Tmax, all_ranks) for p in range(passes)] if return_order else None
     if gathered[0] is None:
-        return (None, None) if return_logp else None
+        res = (None,) + ((None,) if return_logp else ()) + ((None,) if return_order else ())
+        return res if len(res) > 1 else None
     tokens = np.stack(gathered, axis=0).reshape(passes, len(jobs), replicas, L).transpose(1, 0, 2, 3)
-    if not return_logp:
-        return tokens
-    logp = np.ascontiguousarray(np.stack(gathered_lp, axis=0), dtype=np.int32).view(np.float32)
-    return tokens, logp.reshape(passes, len(jobs), replicas, Tmax).transpose(1, 0, 2, 3)
+    res = (tokens,)
+    if return_logp:
+        logp = np.ascontiguousarray(np.stack(gathered_lp, axis=0), dtype=np.int32).view(np.float32)
+        res += (logp.reshape(passes, len(jobs), replicas, Tmax).transpose(1, 0, 2, 3),)
+    if return_order:
+        res += (np.stack(gathered_od, axis=0).astype(np.int32).reshape(passes, len(jobs), replicas, Tmax).transpose(1, 0, 2, 3),)
+    return res if len(res) > 1 else tokens
 
 
 def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.ndarray:
@@ -136,7 +155,8 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
-                           logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1) -> List[List[np.ndarray]]:
+                           logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1,
+                           slot_policy: str = "given") -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -148,7 +168,9 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
 
     ``logp_records``: a list that receives one ``(job index, sweep, replica, T, logp, chosen)`` per sampled row -- logp = the
     row's total log-probability under the distributions this sweep drew from (a re-sweep's value is that sweep's draws given the
-    already filled tokens), chosen = the row was written."""
+    already filled tokens), chosen = the row was written.
+
+    ``slot_policy``: as in ``sample_jobs`` (every sweep starts from the job's ``loc`` as the candidate list)."""
     state = [{"left": want, "tries": tries, "tokens": None, "out": []} for _ in jobs]
     active = [j for j in range(len(jobs)) if want > 0 and tries > 0]
     sweep = 0
@@ -163,6 +185,8 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
             more["temperature"] = temperature
         if int(slots_per_step) != 1:
             more["slots_per_step"] = int(slots_per_step)
+        if slot_policy != "given":
+            more["slot_policy"] = slot_policy
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:

@@ -131,8 +131,13 @@ def draw_orders(loc, orders: int, seed: int, job_id: int) -> np.ndarray:
 
 
 def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout: str = "off", parallel=None,
-               device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None, slots_per_step: int = 1):
+               device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None, slots_per_step: int = 1,
+               slot_policy: str = "given"):
     """Score every job along ``orders`` random visiting orders of its ``loc``.
+
+    ``slot_policy`` = "confident" scores under the confident sampler (model.score): the order is the model's own, found teacher-forced
+    from the candidate list ``loc`` as it stands (only ties ever see the list), so ``orders`` must be 1, the sequential loop runs
+    (``parallel=True`` is a ValueError) and ``order`` in the result is the order taken.  With "given" nothing is passed on.
 
     ``slots_per_step`` = K > 1 scores under the block sampler (model.score); at 1 the calls into the library are the one-slot ones.
 
@@ -144,6 +149,11 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
       logp [J, orders, Tmax] float32 per step, order [J, orders, Tmax] int32 the slot of each step (0-padded)."""
     if orders < 1:
         raise ValueError("orders must be >= 1")
+    if slot_policy not in ("given", "confident"):
+        raise ValueError(f"slot_policy must be 'given' or 'confident', got {slot_policy!r}")
+    confident = slot_policy == "confident"
+    if confident and orders != 1:
+        raise ValueError("slot_policy='confident' takes orders=1: the visiting order is the model's own")
     J = len(jobs)
     n_rows = J * orders
     rank, world, _ = D.env_rank_world()
@@ -153,9 +163,12 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
     jid = np.arange(J, dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
     all_order = np.zeros((J, orders, Tmax), np.int32)
     for j, job in enumerate(jobs):
-        all_order[j, :, :len(job.loc)] = draw_orders(job.loc, orders, seed, int(jid[j]))
+        all_order[j, :, :len(job.loc)] = np.asarray(job.loc, np.int32) if confident else draw_orders(job.loc, orders, seed, int(jid[j]))
     out = np.zeros((hi - lo, Tmax), np.float32)
+    taken = np.zeros((hi - lo, Tmax), np.int32) if confident else None
     more = {} if int(slots_per_step) == 1 else {"slots_per_step": int(slots_per_step)}
+    if confident:
+        more["slot_policy"] = slot_policy
     from .sampler import _id_runs
     pos = np.arange(lo, hi)
     gids = jid[pos // orders] * orders + pos % orders
@@ -169,10 +182,15 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
         chain = np.array([j.chain[0] for j in jb] + [j.chain[1] for j in jb], np.int32) if is_ab else None
         out[cs:ce] = model.score(tok, reg, chain, order, T, dropout=dropout, parallel=parallel, device_batch=device_batch,
                                  seed=seed, row0=int(gids[cs]), **more)
+        if confident:
+            taken[cs:ce] = model.sample_order(len(jb), Tmax)
     # one gather, as for the tokens: the float32 bits travel as int32
     got = D.gather_rows(out.view(np.int32), n_rows, Tmax, all_ranks)
+    got_order = D.gather_rows(taken, n_rows, Tmax, all_ranks) if confident else None
     if got is None:
         return None
+    if confident:
+        all_order = np.ascontiguousarray(got_order, dtype=np.int32).reshape(J, orders, Tmax)
     logp = np.ascontiguousarray(got, dtype=np.int32).view(np.float32).reshape(J, orders, Tmax)
     T = np.array([len(j.loc) for j in jobs], np.int64)
     total = logp.astype(np.float64).sum(axis=2)

@@ -43,6 +43,8 @@
  *   block     (hd_set_slots_per_step, "block decoding" below): everything keyed by `step` in the draw -- the Philox counter word, the
  *             q_noise entry, the guide, target and logp -- stays keyed by the ORDER POSITION t, whatever K is; generated dropout
  *             masks of forward f are keyed by step = f * K, the forward's first position.
+ *   confident (hd_set_slot_policy, "slot policy" below): the session itself permutes order[b, :] forward by forward; the draw at
+ *             position t then meets the noise of position t exactly as above, at the slot the permuted order holds there.
  */
 #ifndef HUDIFF_HIP_H
 #define HUDIFF_HIP_H
@@ -57,7 +59,8 @@ extern "C" {
 #define HD_ABI_VERSION 1      /* layout of HdConfig; rounds 4-5 added entry points only (hd_set_precision, hd_precision_report, hd_precision_reset,
                                  hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
                                  hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
-                                 the struct HdGuide; block decoding added hd_set_slots_per_step */
+                                 the struct HdGuide; block decoding added hd_set_slots_per_step; the slot policy added hd_set_slot_policy and
+                                 hd_sample_order */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -265,6 +268,49 @@ HdStatus hd_set_guide(HdModel* m, const HdGuide* g);   /* NULL clears */
  * -> HD_ERR_INVALID; it enqueues ceil((t1 - t0) / K) forwards.  hd_last_run_ms keeps reporting t1 - t0 in `steps`: the number of
  * forwards timed is ceil(steps / K). */
 HdStatus hd_set_slots_per_step(HdModel* m, int32_t k);
+
+/* ---- slot policy ----------------------------------------------------------------------------------
+ * A session has a slot policy: WHICH slots a forward fills.  HD_SLOTS_GIVEN (default) follows order[b, :] as the caller wrote it.
+ * HD_SLOTS_CONFIDENT, for any block size K in [1, 64], lets the device pick, forward by forward, the K remaining slots of each row
+ * whose distribution is most peaked, from the hidden rows of that very forward.  order[b, 0:T[b]] is then the row's CANDIDATE LIST:
+ * the slots to fill, and the tie-break.
+ *
+ * Forward f, row b, n = min(f * K, T[b]) positions already visited:
+ *   1. for every remaining position i in [n, T[b]), slot s = order[b, i], the 22 values g_j are formed from this forward's hidden row
+ *      exactly as the draw forms them: the raw logits in an unguided session; (z_j + bias_j) / temperature over the allowed tokens in
+ *      a guided one and -inf for the others, with divisor 1 at temperature 0;
+ *   2. the key is c_i = sum_j exp(g_j - max_j g_j) in fp32 (= 1 / max_j p_j: smaller is more confident); a key that is not a finite
+ *      positive number ranks behind every finite one;
+ *   3. the min(K, T[b] - n) positions with the smallest (c_i, i), compared lexicographically, are chosen and become, in ascending
+ *      (c_i, i), positions n, n + 1, ... of the row's order; the positions not chosen follow in their previous relative order (a
+ *      stable partition).  What is keyed by order position -- the target of a scoring session, the guide's allowed bits and bias --
+ *      moves with its entry.  Entries at t >= T[b] are never touched;
+ *   4. the forward's draw then runs as in a given-order block session on the permuted order: position t draws at order[b, t] with the
+ *      noise, guide, target and logp[b, t] of position t.
+ * The selection runs on the device inside the captured step (two launches in front of the draw); nothing is read back.  The forward of
+ * a confident session evaluates the last attention block for every row, at K = 1 too.  Dropout masks, hd_sample_run(t0, t1)
+ * granularity and hd_last_run_ms are those of "block decoding".
+ *
+ * Consequences.  Replay: a HD_SLOTS_GIVEN session with the same K, seed or q_noise, row0, guide and dropout mode, given the realised
+ * order hd_sample_order returns, draws the same tokens and records the same logp bit for bit.  The selection is a deterministic
+ * function of the state, so sum_t logp[b, t] of a recording session is the exact log-likelihood of its tokens under this sampler.  A
+ * scoring session (hd_score_begin) consumes the policy too: teacher-forced, the library picks the order and writes the targets, and
+ * scoring a confident session's tokens from the same candidate list, K, guide and dropout key reproduces its realised order.
+ *
+ * Lifetime: as the block size -- the policy applies to the NEXT hd_sample_begin / hd_sample / hd_score_begin / hd_score, which
+ * consumes it whether it succeeds or fails; hd_sample_restart (which puts the candidate list back) and the guards' repeats keep it;
+ * hd_forward neither uses nor clears it.  hd_set_slot_policy: NULL handle or a value outside {0, 1} -> HD_ERR_INVALID; inside an open
+ * session -> HD_ERR_STATE.  At the begin, confident sessions only: a row whose order[b, 0:T[b]] repeats a slot anywhere ->
+ * HD_ERR_INVALID (the list is a set; the same order stays legal under HD_SLOTS_GIVEN at K = 1); HD_DROPOUT_INJECT ->
+ * HD_ERR_UNSUPPORTED.
+ *
+ * hd_sample_order copies the current order [B, Tmax] of the session out, rows in whole-batch order whatever the lane split: positions
+ * < min(steps run, T[b]) are the visited slots in visiting order; in a HD_SLOTS_GIVEN session it is the order that was given.  Legal
+ * where hd_sample_logp is: inside an open session (it synchronises; HD_ERR_STATE after a guard has fired) and after hd_sample /
+ * hd_sample_end until the next begin, hd_forward or hd_destroy.  No session ever opened, or a NULL handle -> HD_ERR_STATE. */
+enum { HD_SLOTS_GIVEN = 0, HD_SLOTS_CONFIDENT = 1 };
+HdStatus hd_set_slot_policy(HdModel* m, int32_t policy);
+HdStatus hd_sample_order(HdModel* m, int32_t* order /* [B, Tmax] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
