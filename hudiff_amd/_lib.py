@@ -33,6 +33,7 @@ EXPORTS = [
     "hd_set_option", "hd_get_option", "hd_debug_scatter_lnsync",
     "hd_sample_logp", "hd_score_begin", "hd_score", "hd_debug_launch_tally",
     "hd_set_guide", "hd_set_slots_per_step", "hd_set_slot_policy", "hd_sample_order",
+    "hd_set_truncation",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -69,6 +70,11 @@ class HdPrecisionInfo(C.Structure):
 class HdGuide(C.Structure):
     """include/hudiff_hip.h "guided sampling": hd_set_guide copies the arrays; the next begin on the handle consumes the guide."""
     _fields_ = [("B", C.c_int32), ("temperature", C.c_float), ("allow", C.POINTER(C.c_uint32)), ("bias", C.POINTER(C.c_float))]
+
+
+class HdTruncation(C.Structure):
+    """include/hudiff_hip.h "truncated sampling": the next begin on the handle consumes it."""
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
 
 
 class HudiffError(RuntimeError):
@@ -133,6 +139,7 @@ def load():
     lib.hd_set_slots_per_step.argtypes = [vp, C.c_int32]
     lib.hd_set_slot_policy.argtypes = [vp, C.c_int32]
     lib.hd_sample_order.argtypes = [vp, i32p]
+    lib.hd_set_truncation.argtypes = [vp, P(HdTruncation)]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

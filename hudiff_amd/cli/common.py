@@ -64,6 +64,31 @@ def add_guide_args(p):
     return p
 
 
+def add_truncation_args(p):
+    """--top_k / --top_p / --min_p of the four samplers and the scorer (truncated sampling, hudiff_amd/guide.py Truncation); with none
+    of them given the run is the untruncated one."""
+    p.add_argument("--top_k", type=int, default=0,
+                   help="draw only among the k most probable residues of a slot; 0 (default) or 22 = off")
+    p.add_argument("--top_p", type=float, default=1.0,
+                   help="nucleus sampling: draw only among the smallest set of most probable residues whose probability reaches "
+                        "top_p, in (0, 1]; 1 (default) = off")
+    p.add_argument("--min_p", type=float, default=0.0,
+                   help="draw only among residues at least min_p times as probable as the most probable one, in [0, 1]; 0 (default) = off")
+    return p
+
+
+def apply_truncation_args(args, logger=None):
+    """-> {"truncation": Truncation} for sample_jobs[_with_retry] / score_jobs, or {} when the flags cut nothing (the calls are then
+    exactly the untruncated ones).  A value outside its range is a ValueError."""
+    from ..guide import Truncation
+    tr = Truncation(getattr(args, "top_k", 0), getattr(args, "top_p", 1.0), getattr(args, "min_p", 0.0))
+    if tr.neutral:
+        return {}
+    if logger is not None:
+        logger.info("Truncation: top_k {}, top_p {}, min_p {}".format(tr.top_k, tr.top_p, tr.min_p))
+    return {"truncation": tr}
+
+
 def slots_per_step_arg(v):
     k = int(v)
     if not 1 <= k <= 64:
@@ -73,8 +98,8 @@ def slots_per_step_arg(v):
 
 
 def add_block_args(p):
-    """--slots_per_step of the four samplers and the scorer (block decoding, include/hudiff_hip.h); without it, or with 1, the run is
-    the one-slot one."""
+    """--slots_per_step and --slot_policy of the four samplers and the scorer (block decoding, include/hudiff_hip.h); without them, or
+    with 1, the run is the one-slot one.  The truncation flags (add_truncation_args) ride along: the same five commands take them."""
     p.add_argument("--slots_per_step", type=slots_per_step_arg, default=1,
                    help="block decoding: K in [1, 64] slots of a row's visiting order are drawn per denoiser forward, independently "
                         "from that forward's conditionals -- ceil(T / K) forwards per row instead of T; 1 = one slot per forward")
@@ -82,14 +107,14 @@ def add_block_args(p):
                    help="which slots a forward fills: 'given' follows each row's visiting order; 'confident' lets the device pick, in "
                         "every forward, the --slots_per_step remaining slots whose distribution is most peaked (the order is then only "
                         "the list of slots to fill, and the tie-break)")
-    return p
+    return add_truncation_args(p)
 
 
 def apply_block_args(args, jobs, logger=None):
     """-> the keywords for sample_jobs[_with_retry] / score_jobs: {} at K = 1 in the given order (the calls are then exactly the
-    one-slot ones)."""
+    one-slot ones); with truncation flags, plus what apply_truncation_args returns."""
     k = int(args.slots_per_step)
-    more = {}
+    more = apply_truncation_args(args, logger)
     if getattr(args, "slot_policy", "given") != "given":
         more["slot_policy"] = args.slot_policy
         if logger is not None:

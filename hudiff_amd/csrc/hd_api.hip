@@ -223,6 +223,7 @@ struct HdModel {
         int graph_K = -1;                            // slots per step of the captured step (1: pruned tail + sample_step_k; > 1: full last block + sample_block_k)
         const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
         // the guide the captured draw was launched with (GUIDE_*, its temperature -- a kernel argument -- and the buffers it reads)
+        bool graph_trunc = false; TruncP graph_tr{0, 1.f, 0.f};   // truncation of the captured step (its three parameters are kernel arguments)
         int graph_guide = -1; float graph_temp = 1.f; const uint32_t* graph_gallow = nullptr; const float* graph_gbias = nullptr;
         // the T-step loop as ONE graph: `loop_steps` child-graph nodes of `graph` in a chain (hd_sample_run)
         hipGraph_t loop_graph = nullptr;
@@ -264,6 +265,12 @@ struct HdModel {
     // slot policy (include/hudiff_hip.h "slot policy"): hd_set_slot_policy leaves it here; the next begin takes it like the block size
     int policy_next = HD_SLOTS_GIVEN;
     int s_policy = HD_SLOTS_GIVEN;                   // slot policy of the open session
+    // truncated sampling (include/hudiff_hip.h "truncated sampling"): hd_set_truncation leaves the normalised parameters here; the next
+    // begin takes them like the block size.  A truncated session always draws with the guided kernels (s_guide != GUIDE_NONE).
+    bool trunc_pending = false;
+    TruncP trunc_next{0, 1.f, 0.f};
+    bool s_trunc = false;                            // the open session truncates
+    TruncP s_tr{0, 1.f, 0.f};
     bool order_ready = false;                        // the lanes' order buffers hold an ended session's order (hd_sample_order after the end)
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
@@ -638,6 +645,24 @@ extern "C" HdStatus hd_set_slot_policy(HdModel* m, int32_t policy) {
     if (policy != HD_SLOTS_GIVEN && policy != HD_SLOTS_CONFIDENT) return fail(HD_ERR_INVALID, "hd_set_slot_policy: unknown policy %d", policy);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slot_policy: a sampling session is open (the policy belongs to the NEXT begin)");
     m->policy_next = policy;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "truncated sampling": validates and normalises; the next begin takes it.  All three cuts off == cleared.
+extern "C" HdStatus hd_set_truncation(HdModel* m, const HdTruncation* t) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_truncation: null model");
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_truncation: a sampling session is open (the truncation belongs to the NEXT begin)");
+    m->trunc_pending = false;
+    m->trunc_next = TruncP{0, 1.f, 0.f};
+    if (!t) return HD_OK;
+    if (t->top_k < 0 || t->top_k > 22) return fail(HD_ERR_INVALID, "hd_set_truncation: top_k = %d outside [0, 22]", t->top_k);
+    if (!(t->top_p > 0.f && t->top_p <= 1.f))        // (NaN fails every comparison)
+        return fail(HD_ERR_INVALID, "hd_set_truncation: top_p = %g outside (0, 1]", (double)t->top_p);
+    if (!(t->min_p >= 0.f && t->min_p <= 1.f)) return fail(HD_ERR_INVALID, "hd_set_truncation: min_p = %g outside [0, 1]", (double)t->min_p);
+    const TruncP tr{t->top_k >= 22 ? 0 : t->top_k, t->top_p, t->min_p};
+    if (tr.top_k == 0 && tr.top_p >= 1.f && tr.min_p == 0.f) return HD_OK;      // nothing is cut: the session launches the kernels it always did
+    m->trunc_next = tr;
+    m->trunc_pending = true;
     return HD_OK;
 }
 
@@ -1810,7 +1835,18 @@ static HdStatus block_draw(HdModel* m, const Segs& sg) {
     Workspace& ws = ln.ws;
     const float* qn = m->s_has_q ? m->qnoise : nullptr;
     const dim3 grid(sg.B, m->sK), block(64 * SS_WAVES);
-    if (m->s_guide != GUIDE_NONE) {
+    if (m->s_trunc) {                                // (a truncated session is always guided: sample_begin_impl)
+        const GuideTP g{GuideP{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp}, m->s_tr};
+        if (m->s_mode == DRAW_SAMPLE)
+            hipLaunchKernelGGL((sample_block_guided_k<DRAW_SAMPLE, true>), grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, (float*)nullptr, (const int32_t*)nullptr, g);
+        else if (m->s_mode == DRAW_RECORD)
+            hipLaunchKernelGGL((sample_block_guided_k<DRAW_RECORD, true>), grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
+        else
+            hipLaunchKernelGGL((sample_block_guided_k<DRAW_SCORE, true>), grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
+    } else if (m->s_guide != GUIDE_NONE) {
         const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
         if (m->s_mode == DRAW_SAMPLE)
             hipLaunchKernelGGL(sample_block_guided_k<DRAW_SAMPLE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
@@ -1845,7 +1881,13 @@ static HdStatus slot_choose(HdModel* m, const Segs& sg) {
     const dim3 cgrid((npos + SC_WAVES - 1) / SC_WAVES, sg.B), cblock(64 * SC_WAVES);
     const size_t lds = (size_t)SC_HALF * m->D * sizeof(float);
     int32_t* tg = m->s_mode == DRAW_SCORE ? ws.target : nullptr;
-    if (m->s_guide != GUIDE_NONE) {
+    if (m->s_trunc) {
+        const GuideTP g{GuideP{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp}, m->s_tr};
+        hipLaunchKernelGGL((slot_conf_k<true, true>), cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf, g);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(slot_select_k<true>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, tg, ws.T, m->sTmax, m->sK, ln.rs, ws.conf,
+                           ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : (float*)nullptr);
+    } else if (m->s_guide != GUIDE_NONE) {
         const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
         hipLaunchKernelGGL(slot_conf_k<true>, cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf, g);
         HIP_TRY(hipGetLastError());
@@ -1876,7 +1918,20 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
     // (the last workgroup of sample_step_k advances the step)
     const float* hm = prune ? ws.Xc : ws.Y;
     const float* qn = m->s_has_q ? m->qnoise : nullptr;
-    if (m->s_guide != GUIDE_NONE) {
+    if (m->s_trunc) {
+        const GuideTP g{GuideP{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp}, m->s_tr};
+        const dim3 grid(sg.B), block(64 * SS_WAVES);
+        const int compact = prune ? 1 : 0;
+        if (m->s_mode == DRAW_SAMPLE)
+            hipLaunchKernelGGL((sample_step_guided_k<DRAW_SAMPLE, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, (float*)nullptr, (const int32_t*)nullptr, g);
+        else if (m->s_mode == DRAW_RECORD)
+            hipLaunchKernelGGL((sample_step_guided_k<DRAW_RECORD, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
+        else
+            hipLaunchKernelGGL((sample_step_guided_k<DRAW_SCORE, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
+                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
+    } else if (m->s_guide != GUIDE_NONE) {
         const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
         const dim3 grid(sg.B), block(64 * SS_WAVES);
         const int compact = prune ? 1 : 0;
@@ -1906,7 +1961,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                   uint64_t seed, uint64_t row0, const float* q_noise,
                                   const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide, int K,
-                                  int policy) {
+                                  int policy, const TruncP* trunc) {
     if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -1921,6 +1976,11 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
     m->sK = 1;
     m->s_policy = HD_SLOTS_GIVEN;
+    m->s_trunc = false; m->s_tr = TruncP{0, 1.f, 0.f};
+    // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
+    // bias, temperature 1), under which g_j == logit_j bit for bit
+    HdModel::Guide neutral;
+    if (trunc && !guide) { neutral.B = B; guide = &neutral; }
     const bool confident = policy == HD_SLOTS_CONFIDENT;
     if (confident && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
         return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop in the given order; a "
@@ -1933,7 +1993,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
         if (score && guide->temperature == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
     }
-    if (B == 0) { m->sK = K; m->s_policy = policy; m->in_session = true; return HD_OK; }
+    if (B == 0) { m->sK = K; m->s_policy = policy; m->in_session = true; return HD_OK; }      // (no row: nothing to guide or truncate)
     HD_TRY(validate_inputs(m, tokens, region, chain, B));
     for (int b = 0; b < B; ++b) {
         if (T[b] < 0 || T[b] > Tmax) return fail(HD_ERR_INVALID, "T[%d] = %d out of [0,%d]", b, T[b], Tmax);
@@ -2113,6 +2173,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     if (guide) { m->s_guide = guide->has_bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW; m->s_temp = guide->temperature; }
     m->sK = K;
     m->s_policy = policy;
+    if (trunc) { m->s_trunc = true; m->s_tr = *trunc; }
     m->in_session = true;
     return HD_OK;
 }
@@ -2142,6 +2203,15 @@ static int take_slot_policy(HdModel* m) {
     return p;
 }
 
+// And the truncation hd_set_truncation left.
+static bool take_truncation(HdModel* m, TruncP* tr) {
+    if (!m || !m->trunc_pending) return false;
+    *tr = m->trunc_next;
+    m->trunc_next = TruncP{0, 1.f, 0.f};
+    m->trunc_pending = false;
+    return true;
+}
+
 extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                     const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                     uint64_t seed, uint64_t row0, const float* q_noise,
@@ -2151,10 +2221,14 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
     const bool was_open = m && m->in_session;
     const int K = take_slots_per_step(m);
     const int policy = take_slot_policy(m);
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K, policy);
+    TruncP tr;
+    const bool truncated = take_truncation(m, &tr);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K, policy,
+                                         truncated ? &tr : nullptr);
     if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
         m->s_policy = HD_SLOTS_GIVEN;
+        m->s_trunc = false;
     }
     return s;
 }
@@ -2169,10 +2243,14 @@ extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int3
     const bool was_open = m && m->in_session;
     const int K = take_slots_per_step(m);
     const int policy = take_slot_policy(m);
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K, policy);
+    TruncP tr;
+    const bool truncated = take_truncation(m, &tr);
+    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K, policy,
+                                         truncated ? &tr : nullptr);
     if (s != HD_OK && m && !was_open) {
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
         m->s_policy = HD_SLOTS_GIVEN;
+        m->s_trunc = false;
     }
     return s;
 }
@@ -2227,7 +2305,8 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
             ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K || ln.graph_policy != m->s_policy ||
             ln.graph_guide != m->s_guide || (m->s_guide != GUIDE_NONE && (ln.graph_temp != m->s_temp || ln.graph_gallow != ln.ws.gallow)) ||
-            (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias)) {
+            (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias) || ln.graph_trunc != m->s_trunc ||
+            (m->s_trunc && (ln.graph_tr.top_k != m->s_tr.top_k || ln.graph_tr.top_p != m->s_tr.top_p || ln.graph_tr.min_p != m->s_tr.min_p))) {
             ln.drop_graphs();
             HIP_TRY(hipStreamSynchronize(ln.stream));
             HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
@@ -2240,6 +2319,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
             ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K; ln.graph_policy = m->s_policy;
             ln.graph_guide = m->s_guide; ln.graph_temp = m->s_temp; ln.graph_gallow = ln.ws.gallow; ln.graph_gbias = ln.ws.gbias;
+            ln.graph_trunc = m->s_trunc; ln.graph_tr = m->s_tr;
         }
     }
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipEventRecord(m->lane[l].ev0, m->lane[l].stream));

@@ -2494,12 +2494,44 @@ struct GuideP {
     float temperature;       // 0 = greedy
 };
 enum { DRAW_SAMPLE = 0, DRAW_RECORD = 1, DRAW_SCORE = 2 };
-template <int NW, int MODE = DRAW_SAMPLE, bool GUIDED = false>
+
+// TRUNC (compile time; hd_set_truncation, include/hudiff_hip.h "truncated sampling"): top-k / top-p / min-p cut of the 22-token
+// distribution in front of the draw.  A truncated session always runs the GUIDED form (a session without a guide gets every bit, no bias
+// and temperature 1, which is g_j == logit_j bit for bit), so the cut works on g.  The host normalises the three parameters: top_k in
+// [1, 21] or 0 = off, top_p in (0, 1) or >= 1 = off, min_p in (0, 1] or 0 = off.
+struct TruncP { int top_k; float top_p; float min_p; };
+struct GuideTP { GuideP g; TruncP tr; };                 // the kernel argument of a truncating instantiation
+template <bool TRUNC> using GuideArg = std::conditional_t<TRUNC, GuideTP, GuideP>;
+
+// The keep-set, for the draw (sample_row) and for the confidence key (slot_conf_k) alike.  Called by a whole wave; lane j < 22 holds
+// token j: g (-inf when not allowed), e = expf(g - max g) (0 when not allowed), and esum = wave_sum(e).  22 pairs of broadcast shuffles in
+// ascending token index give every lane its rank on g (ties: the lower index is ahead) and `before`, the fp32 sum of e over the tokens
+// ahead of it, accumulated in that order: no atomics, no LDS, the same bits on every run.  The rank-0 token is always kept.
+__device__ __forceinline__ bool trunc_keep(float g, float e, bool allowed, float esum, int lane, const TruncP& tr) {
+    const unsigned long long am = __ballot(allowed);
+    int rank = 0;
+    float before = 0.f;
+#pragma unroll
+    for (int i = 0; i < 22; ++i) {
+        const float gi = __shfl(g, i), ei = __shfl(e, i);
+        const bool ahead = ((am >> i) & 1ull) && (gi > g || (gi == g && i < lane));
+        rank += ahead ? 1 : 0;
+        before += ahead ? ei : 0.f;
+    }
+    bool keep = allowed;
+    if (tr.top_k > 0) keep = keep && rank < tr.top_k;
+    if (tr.top_p < 1.f) keep = keep && before < tr.top_p * esum;
+    if (tr.min_p > 0.f) keep = keep && e >= tr.min_p;
+    return keep || (allowed && rank == 0);
+}
+
+template <int NW, int MODE = DRAW_SAMPLE, bool GUIDED = false, bool TRUNC = false>
 __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w, int32_t* __restrict__ tokens, int b, int slot, uint32_t t,
                                            const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
                                            float* lg, float* __restrict__ logp_out = nullptr, int target = 0,
                                            const uint32_t* __restrict__ g_allow = nullptr, const float* __restrict__ g_bias = nullptr,
-                                           float g_temp = 1.f) {
+                                           float g_temp = 1.f, [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
+    static_assert(GUIDED || !TRUNC, "a truncated session runs the guided form");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the guide of this (row, step): asked for before the decoder's dot products, used behind them (wave 0, lane j = token j)
     [[maybe_unused]] bool allowed = true;
@@ -2538,15 +2570,25 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     }
     const float mx = wave_max(mylogit);
     const float e = (lane < 22) ? expf(mylogit - mx) : 0.f;
-    const float esum = wave_sum(e);
+    float esum = wave_sum(e);
     // a NaN / infinite logit makes the sum NaN (the reference's torch.multinomial raises on such a row, sample.py:512); the
     // step still writes a token, hd_sample_end reports the flag
     if (lane == 0 && !(esum > 0.f && esum < INFINITY)) atomicOr(const_cast<uint32_t*>(&rs->pad[0]), 1u);
+    // TRUNC: from here on the sum is that of the kept tokens (the flag above is raised from the full one)
+    [[maybe_unused]] bool kept = true;
+    if constexpr (TRUNC) {
+        kept = trunc_keep(mylogit, e, allowed, esum, lane, tr);
+        esum = wave_sum(kept ? e : 0.f);
+    }
     if constexpr (MODE == DRAW_SCORE) {
         const float zt = __shfl(mylogit, target & 31);
+        [[maybe_unused]] int kt = 1;
+        if constexpr (TRUNC) kt = __shfl(kept ? 1 : 0, target & 31);
         if (lane == 0) {
             tokens[(long)b * L + slot] = target;
-            *logp_out = (zt - mx) - logf(esum);
+            float lp = (zt - mx) - logf(esum);
+            if constexpr (TRUNC) lp = kt ? lp : -INFINITY;   // a target the cut removed has probability 0 under this sampler
+            *logp_out = lp;
         }
         return;
     }
@@ -2566,6 +2608,7 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     }
     float ratio = (lane < 22) ? p / q : -INFINITY;
     if constexpr (GUIDED) ratio = !allowed ? -INFINITY : greedy ? mylogit : ratio;
+    if constexpr (TRUNC) ratio = kept ? ratio : -INFINITY;
     int best = lane;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -2584,13 +2627,14 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
 // one-thread launch per step that advance_step_k was.
 // logp / target: [B, Tmax] of the lane (row b at step t), used by the recording and the teacher-forced kernel below only.
 constexpr int SS_WAVES = 16;
-template <int MODE, bool GUIDED = false>
+template <int MODE, bool GUIDED = false, bool TRUNC = false>
 __device__ __forceinline__ void sample_step_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
                                                  const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
                                                  const float* __restrict__ q_noise, int q_rows, int q_off,
                                                  RunState* __restrict__ rs, const Segs& sg, int compact, int advance,
                                                  float* __restrict__ logp, const int32_t* __restrict__ target,
-                                                 [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f}) {
+                                                 [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f},
+                                                 [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
     __shared__ float lg[32];
     const int b = blockIdx.x;
     const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2600,9 +2644,9 @@ __device__ __forceinline__ void sample_step_body(const float* __restrict__ Hm, i
         const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
         if constexpr (GUIDED) {
             const long bt = (long)b * Tmax + t;
-            sample_row<SS_WAVES, MODE, true>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
-                                             MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
-                                             g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature);
+            sample_row<SS_WAVES, MODE, true, TRUNC>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
+                                                    MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
+                                                    g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr);
         } else if constexpr (MODE == DRAW_SAMPLE)
             sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
         else
@@ -2642,16 +2686,21 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_logp_k(const float*
 }
 
 // The step of a GUIDED session (hd_set_guide) in any of the three draw modes; logp / target may be nullptr in DRAW_SAMPLE.  Sessions
-// without a guide never launch it.
-template <int MODE>
+// without a guide never launch it.  TRUNC: the step of a truncated session (hd_set_truncation), guided or not; the argument then carries
+// the three cut parameters behind the guide, and the instantiations without it are what they were.
+template <int MODE, bool TRUNC = false>
 __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_guided_k(const float* __restrict__ Hm, int D, HeadW w,
                                                      int32_t* __restrict__ tokens,
                                                      const int32_t* __restrict__ order,
                                                      const int32_t* __restrict__ T, int Tmax,
                                                      const float* __restrict__ q_noise, int q_rows, int q_off,
                                                      RunState* __restrict__ rs, Segs sg, int compact, int advance,
-                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideP g) {
-    sample_step_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target, g);
+                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideArg<TRUNC> g) {
+    if constexpr (TRUNC)
+        sample_step_body<MODE, true, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target,
+                                           g.g, g.tr);
+    else
+        sample_step_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2662,13 +2711,14 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_guided_k(const floa
 // write one token.  The last workgroup of the whole grid to finish stores step + K; every workgroup has read `step` before it
 // increments `done`.
 // ------------------------------------------------------------------------------------------------
-template <int MODE, bool GUIDED = false>
+template <int MODE, bool GUIDED = false, bool TRUNC = false>
 __device__ __forceinline__ void sample_block_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
                                                   const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
                                                   const float* __restrict__ q_noise, int q_rows, int q_off,
                                                   RunState* __restrict__ rs, const Segs& sg,
                                                   float* __restrict__ logp, const int32_t* __restrict__ target,
-                                                  [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f}) {
+                                                  [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f},
+                                                  [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
     __shared__ float lg[32];
     const int b = blockIdx.x;
     const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2678,9 +2728,9 @@ __device__ __forceinline__ void sample_block_body(const float* __restrict__ Hm, 
         const int slot = order[bt];
         const float* x = Hm + (long)sg.row(b, slot) * D;
         if constexpr (GUIDED)
-            sample_row<SS_WAVES, MODE, true>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
-                                             MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
-                                             g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature);
+            sample_row<SS_WAVES, MODE, true, TRUNC>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
+                                                    MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
+                                                    g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr);
         else if constexpr (MODE == DRAW_SAMPLE)
             sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
         else
@@ -2716,15 +2766,18 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_block_logp_k(const float
     static_assert(MODE == DRAW_RECORD || MODE == DRAW_SCORE, "the plain draw is sample_block_k");
     sample_block_body<MODE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target);
 }
-template <int MODE>
+template <int MODE, bool TRUNC = false>
 __global__ void __launch_bounds__(64 * SS_WAVES) sample_block_guided_k(const float* __restrict__ Hm, int D, HeadW w,
                                                      int32_t* __restrict__ tokens,
                                                      const int32_t* __restrict__ order,
                                                      const int32_t* __restrict__ T, int Tmax,
                                                      const float* __restrict__ q_noise, int q_rows, int q_off,
                                                      RunState* __restrict__ rs, Segs sg,
-                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideP g) {
-    sample_block_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g);
+                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideArg<TRUNC> g) {
+    if constexpr (TRUNC)
+        sample_block_body<MODE, true, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g.g, g.tr);
+    else
+        sample_block_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2737,15 +2790,17 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_block_guided_k(const flo
 // does) and takes the 22 decoder dot products against weights staged in LDS -- 11 decoder rows at a time (11 * D floats <= 44 KiB), so
 // the 22 * D weights are read from L2 once per workgroup, not once per position.  Lane j < 22 then holds g_j (the guide applied as
 // sample_row applies it) and the key is c = sum_j exp(g_j - max_j g_j) = 1 / max_j p_j in fp32: butterfly reductions in a fixed order,
-// no atomics, so a session repeats bit for bit.  conf [B, Tmax] of the lane.
+// no atomics, so a session repeats bit for bit.  conf [B, Tmax] of the lane.  TRUNC (a truncated session, always GUIDED): the key is
+// the sum over the kept tokens, c = esum' = 1 / max_j p'_j, with the keep-set of the draw (trunc_keep).
 // ------------------------------------------------------------------------------------------------
 constexpr int SC_WAVES = 16;
 constexpr int SC_HALF = 11;                              // decoder rows staged per pass (2 passes = the 22 tokens of the draw)
-template <bool GUIDED>
+template <bool GUIDED, bool TRUNC = false>
 __global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __restrict__ Hm, int D, HeadW w,
                                                    const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
                                                    const RunState* __restrict__ rs, Segs sg, float* __restrict__ conf,
-                                                   [[maybe_unused]] GuideP g) {
+                                                   [[maybe_unused]] GuideArg<TRUNC> ga) {
+    static_assert(GUIDED || !TRUNC, "a truncated session runs the guided form");
     extern __shared__ float sc_w[];                      // [SC_HALF, D]
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2776,8 +2831,11 @@ __global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __rest
         }
     }
     if (!live) return;
+    [[maybe_unused]] bool allowed = lane < 22;
     if constexpr (GUIDED) {
-        const bool allowed = lane < 22 && ((g.allow[bi] >> lane) & 1u);
+        GuideP g;
+        if constexpr (TRUNC) g = ga.g; else g = ga;
+        allowed = lane < 22 && ((g.allow[bi] >> lane) & 1u);
         if (allowed) {
             if (g.bias) z += g.bias[bi * 22 + lane];
             z = z / (g.temperature == 0.f ? 1.f : g.temperature);
@@ -2786,7 +2844,9 @@ __global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __rest
         }
     }
     const float mx = wave_max(z);
-    const float c = wave_sum(lane < 22 ? expf(z - mx) : 0.f);
+    const float e = lane < 22 ? expf(z - mx) : 0.f;
+    float c = wave_sum(e);
+    if constexpr (TRUNC) c = wave_sum(trunc_keep(z, e, allowed, c, lane, ga.tr) ? e : 0.f);
     if (lane == 0) conf[bi] = c;
 }
 

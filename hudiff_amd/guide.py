@@ -11,6 +11,9 @@ token's under the temperature-1 guided distribution.
 
 A ``Guide`` is what ``model.sample(..., guide=)`` / ``model.score(..., guide=)`` and ``sampler.Job.guide`` take; ``guided_log_probs`` is
 the same definition in numpy float64 for host-side users; ``parse_constraints`` reads the text form of the CLIs' ``--constraints_fpath``.
+
+A ``Truncation`` (top_k, top_p, min_p; include/hudiff_hip.h "truncated sampling") cuts the tail of that distribution in front of the
+draw; ``truncation_keep`` is its keep-set in float64, and ``guided_log_probs`` / ``confidence_keys`` take it as ``truncation=``.
 """
 from __future__ import annotations
 
@@ -86,10 +89,69 @@ class Guide:
         return Guide(allow, bias, temperature)
 
 
-def guided_log_probs(logits22, allow, bias=None, temperature=1.0):
+class Truncation:
+    """top_k: keep the k best tokens (0 or >= 22 = off); top_p: keep the smallest head whose probability mass reaches top_p (in
+    (0, 1], 1 = off); min_p: keep the tokens with p >= min_p * p_max (in [0, 1], 0 = off).  The best token always stays.  Validates
+    as hd_set_truncation does; ``neutral`` = nothing is cut (such a truncation is never handed to the library)."""
+
+    def __init__(self, top_k=0, top_p=1.0, min_p=0.0):
+        if isinstance(top_k, (bool, float)) or int(top_k) != top_k or not 0 <= int(top_k) <= N_DRAW:
+            raise ValueError(f"top_k must be an integer in [0, {N_DRAW}], got {top_k!r}")
+        top_p, min_p = float(top_p), float(min_p)
+        if not 0.0 < top_p <= 1.0:                   # (NaN fails every comparison)
+            raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+        self.top_k, self.top_p, self.min_p = int(top_k), top_p, min_p
+
+    @property
+    def neutral(self):
+        return self.top_k in (0, N_DRAW) and self.top_p >= 1.0 and self.min_p == 0.0
+
+    def __eq__(self, other):
+        return isinstance(other, Truncation) and (self.top_k, self.top_p, self.min_p) == (other.top_k, other.top_p, other.min_p)
+
+    def __hash__(self):
+        return hash((self.top_k, self.top_p, self.min_p))
+
+    def __repr__(self):
+        return f"Truncation(top_k={self.top_k}, top_p={self.top_p}, min_p={self.min_p})"
+
+
+def truncation_keep(g22, truncation):
+    """The keep-set of include/hudiff_hip.h "truncated sampling" in numpy float64: g22 [..., 22] are the values the draw forms (-inf =
+    not allowed) -> bool [..., 22].  Tokens are ranked on g, the lower index first among equals; token j is kept when it is allowed,
+    its rank is below top_k, the mass of the tokens ranked ahead of it is below top_p of the whole and exp(g_j - max g) >= min_p; the
+    best token is always kept.  ``truncation`` None or neutral keeps every allowed token."""
+    g = np.asarray(g22, np.float64)
+    if g.shape[-1] != N_DRAW:
+        raise ValueError(f"g22 must end in {N_DRAW} tokens, got {g.shape}")
+    allowed = g > -np.inf
+    if truncation is None or truncation.neutral:
+        return allowed
+    with np.errstate(invalid="ignore"):
+        e = np.where(allowed, np.exp(g - g.max(axis=-1, keepdims=True)), 0.0)
+    idx = np.arange(N_DRAW)
+    # ahead[..., j, i]: token i is ranked ahead of token j
+    gj, gi = g[..., :, None], g[..., None, :]
+    ahead = allowed[..., None, :] & ((gi > gj) | ((gi == gj) & (idx[None, :] < idx[:, None])))
+    rank = ahead.sum(axis=-1)
+    before = np.where(ahead, e[..., None, :], 0.0).sum(axis=-1)
+    keep = allowed.copy()
+    if 0 < truncation.top_k < N_DRAW:
+        keep &= rank < truncation.top_k
+    if truncation.top_p < 1.0:
+        keep &= before < truncation.top_p * e.sum(axis=-1, keepdims=True)
+    if truncation.min_p > 0.0:
+        keep &= e >= truncation.min_p
+    return keep | (allowed & (rank == 0))
+
+
+def guided_log_probs(logits22, allow, bias=None, temperature=1.0, truncation=None):
     """The definition in numpy float64: logits22 [..., 22], allow [...] (uint32 bits), bias [..., 22] or None -> log p [..., 22],
     -inf where a token is not allowed.  temperature == 0 (greedy) gives the temperature-1 distribution, the one a greedy session
-    records its log-probabilities under; the greedy token is the argmax of the result."""
+    records its log-probabilities under; the greedy token is the argmax of the result.  ``truncation`` (a Truncation): the
+    distribution is renormalised over ``truncation_keep`` and -inf for the tokens that are not kept, too."""
     z = np.asarray(logits22, np.float64)
     if z.shape[-1] != N_DRAW:
         raise ValueError(f"logits22 must end in {N_DRAW} tokens, got {z.shape}")
@@ -100,17 +162,20 @@ def guided_log_probs(logits22, allow, bias=None, temperature=1.0):
         z = z / tp
     ok = ((np.asarray(allow, np.int64)[..., None] >> np.arange(N_DRAW)) & 1).astype(bool)
     g = np.where(ok, z, -np.inf)
+    if truncation is not None and not truncation.neutral:
+        g = np.where(truncation_keep(g, truncation), g, -np.inf)
     mx = g.max(axis=-1, keepdims=True)
     with np.errstate(divide="ignore"):
         return (g - mx) - np.log(np.exp(g - mx).sum(axis=-1, keepdims=True))
 
 
-def confidence_keys(logits, allow=None, bias=None, temperature=1.0):
+def confidence_keys(logits, allow=None, bias=None, temperature=1.0, truncation=None):
     """The key of slot_policy="confident" (include/hudiff_hip.h "slot policy") in numpy float64: logits [..., >= 22] (the first 22
     tokens are the draw's), allow [...] uint32 bits or None (everything allowed), bias [..., 22] or None -> log c [...], with
         c = sum_j exp(g_j - max_j g_j) = 1 / max_j p_j,   g_j = (z_j + bias_j) / temperature over the allowed tokens, -inf elsewhere
     (divisor 1 at temperature 0, as the draw).  Smaller is more confident.  A slot whose c is not a finite positive number -- a NaN
-    or +inf logit, nothing allowed -- gets +inf: it ranks behind every finite key."""
+    or +inf logit, nothing allowed -- gets +inf: it ranks behind every finite key.  ``truncation`` (a Truncation): the sum runs over
+    ``truncation_keep`` only, c = 1 / max_j p'_j of the truncated distribution."""
     z = np.asarray(logits, np.float64)[..., :N_DRAW]
     if z.shape[-1] != N_DRAW:
         raise ValueError(f"logits must end in at least {N_DRAW} tokens, got {z.shape}")
@@ -123,6 +188,8 @@ def confidence_keys(logits, allow=None, bias=None, temperature=1.0):
         ok = ((np.asarray(allow, np.int64)[..., None] >> np.arange(N_DRAW)) & 1).astype(bool)
         z = np.where(ok, z, -np.inf)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if truncation is not None and not truncation.neutral:
+            z = np.where(truncation_keep(z, truncation), z, -np.inf)
         c = np.exp(z - z.max(axis=-1, keepdims=True)).sum(axis=-1)
         good = np.isfinite(c) & (c > 0)
         return np.where(good, np.log(np.where(good, c, 1.0)), np.inf)

@@ -281,6 +281,16 @@ class _Denoiser:
         score_begin on this handle, which consumes it whether it succeeds or fails."""
         L.check(self._lib.hd_set_slot_policy(self._h, self._policy_id(policy)))
 
+    def set_truncation(self, truncation):
+        """hd_set_truncation: the top-k / top-p / min-p cut (hudiff_amd.guide.Truncation; None clears) of the NEXT sample /
+        sample_begin / score / score_begin on this handle, which consumes it whether it succeeds or fails (include/hudiff_hip.h
+        "truncated sampling")."""
+        if truncation is None:
+            L.check(self._lib.hd_set_truncation(self._h, None))
+            return
+        t = L.HdTruncation(int(truncation.top_k), float(truncation.top_p), float(truncation.min_p))
+        L.check(self._lib.hd_set_truncation(self._h, C.byref(t)))
+
     @staticmethod
     def _policy_id(policy):
         if isinstance(policy, str):
@@ -298,16 +308,19 @@ class _Denoiser:
         L.check(self._lib.hd_sample_order(self._h, L.ptr(order, C.c_int32)))
         return order
 
-    def _arm(self, guide, B, slots_per_step, slot_policy="given"):
+    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None):
         """What the next begin consumes: the block size (the library is told only when it is not 1), the slot policy (told only when
-        it is not "given") and the guide."""
+        it is not "given"), the truncation (told only when it cuts something) and the guide."""
         policy = self._policy_id(slot_policy)
         block = int(slots_per_step) != 1
+        trunc = truncation is not None and not truncation.neutral
         if block:
             self.set_slots_per_step(slots_per_step)
         try:
             if policy != L.HD_SLOTS_GIVEN:
                 L.check(self._lib.hd_set_slot_policy(self._h, policy))
+            if trunc:
+                self.set_truncation(truncation)
             if guide is not None:
                 self.set_guide(guide, B)
         except Exception:
@@ -315,11 +328,13 @@ class _Denoiser:
                 self.set_slots_per_step(1)           # (no begin will follow to consume it)
             if policy != L.HD_SLOTS_GIVEN:
                 self._lib.hd_set_slot_policy(self._h, L.HD_SLOTS_GIVEN)
+            if trunc:
+                self._lib.hd_set_truncation(self._h, None)
             raise
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1,
-               slot_policy="given"):
+               slot_policy="given", truncation=None):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
@@ -332,13 +347,17 @@ class _Denoiser:
         list (no slot twice) and lets the device fill, in every forward, the K remaining slots whose distribution is most peaked in
         that forward (include/hudiff_hip.h "slot policy"); ``sample_order()`` afterwards returns the order taken.
 
+        ``truncation``: a hudiff_amd.guide.Truncation (top_k, top_p, min_p) for this call only: every draw is taken from its
+        distribution cut to the kept tokens and renormalised, and a recorded logp is the token's under that distribution.  None or a
+        neutral one (nothing cut) makes no call into the library.
+
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
         are the same with and without it."""
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
-        self._arm(guide, B, slots_per_step, slot_policy)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation)
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
@@ -361,9 +380,10 @@ class _Denoiser:
         return logp
 
     # -- likelihood of given sequences -------------------------------------------------------------
-    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given"):
+    def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given",
+                   truncation=None):
         logp = np.zeros((B, Tmax), dtype=np.float32)
-        self._arm(guide, B, slots_per_step, slot_policy)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation)
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
@@ -372,7 +392,8 @@ class _Denoiser:
         return logp
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
-              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given"):
+              enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given",
+              truncation=None):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -384,6 +405,10 @@ class _Denoiser:
 
         ``guide``: the values are log-probabilities under the guided distribution (hudiff_amd.guide); a token its slot does not allow,
         or temperature 0, is an error.  Step-parallel: an expanded row takes the guide of the row it came from.
+
+        ``truncation``: the values are log-probabilities under the truncated distribution (hudiff_amd.guide.Truncation); a token the
+        cut of its step removes has probability 0 under that sampler and scores -inf (no error).  Step-parallel: every expanded
+        session gets the same truncation.
 
         ``slots_per_step`` = K > 1: the log-likelihood under the block sampler -- logp[b, t] is conditioned on the tokens with
         ``order[b, (t // K) * K : T[b]]`` masked (the whole group of t, not only t onwards), which is what a sampling session with
@@ -406,7 +431,7 @@ class _Denoiser:
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
         flags = self._flags(dropout, graph, prune, lanes)
         if not parallel:
-            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy)
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy, truncation)
         else:
             from . import scoring
             x = scoring.expand_steps(tok, reg, chn, order, T, slots_per_step=K)      # (K outside [1, 64]: ValueError)
@@ -424,7 +449,8 @@ class _Denoiser:
                 ch = None if x.chain is None else np.ascontiguousarray(np.concatenate([x.chain[s:e], x.chain[n + s:n + e]]))
                 flat[s:e] = self._score_seq(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
                                             np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, K, flags,
-                                            seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]), K)
+                                            seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]), K,
+                                            truncation=truncation)
             logp = x.fold(flat, Tmax)
         if was_torch:
             import torch
@@ -432,11 +458,11 @@ class _Denoiser:
         return logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given"):
+                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
         last_run_ms / sample_logp work on it as on a sampling session."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
@@ -445,10 +471,10 @@ class _Denoiser:
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                      enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1,
-                     slot_policy="given"):
+                     slot_policy="given", truncation=None):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),

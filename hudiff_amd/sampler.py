@@ -51,7 +51,7 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
                 job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1,
-                slot_policy: str = "given", return_order: bool = False):
+                slot_policy: str = "given", return_order: bool = False, truncation=None):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -71,6 +71,9 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     ``slot_policy`` = "confident": every row's ``loc`` is its candidate list and the device picks, forward by forward, the K slots
     it is surest about (model.sample); with "given" nothing is passed on and the calls into the library are exactly today's.
 
+    ``truncation``: a hudiff_amd.guide.Truncation (top_k, top_p, min_p) for every draw of every row (model.sample); None or a neutral
+    one passes nothing on and the calls into the library are exactly today's.
+
     ``return_order``: also returns (last) int32 [len(jobs), passes, replicas, Tmax], the order each row took (model.sample_order;
     under "given" the order it was handed), gathered like the log-probabilities."""
     if slot_policy not in ("given", "confident"):
@@ -89,6 +92,8 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
         more["slots_per_step"] = int(slots_per_step)
     if slot_policy != "given":
         more["slot_policy"] = slot_policy
+    if truncation is not None and not truncation.neutral:
+        more["truncation"] = truncation
     od = np.zeros((passes, hi - lo, Tmax), np.int32) if return_order else None
     jid = np.arange(len(jobs), dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
     pos = np.arange(lo, hi)                                      # positions in the packed (job-major) row list
@@ -156,7 +161,7 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
                            logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1,
-                           slot_policy: str = "given") -> List[List[np.ndarray]]:
+                           slot_policy: str = "given", truncation=None) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -170,7 +175,9 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
     row's total log-probability under the distributions this sweep drew from (a re-sweep's value is that sweep's draws given the
     already filled tokens), chosen = the row was written.
 
-    ``slot_policy``: as in ``sample_jobs`` (every sweep starts from the job's ``loc`` as the candidate list)."""
+    ``slot_policy``: as in ``sample_jobs`` (every sweep starts from the job's ``loc`` as the candidate list).
+
+    ``truncation``: as in ``sample_jobs``, for every sweep."""
     state = [{"left": want, "tries": tries, "tokens": None, "out": []} for _ in jobs]
     active = [j for j in range(len(jobs)) if want > 0 and tries > 0]
     sweep = 0
@@ -187,6 +194,8 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
             more["slots_per_step"] = int(slots_per_step)
         if slot_policy != "given":
             more["slot_policy"] = slot_policy
+        if truncation is not None and not truncation.neutral:
+            more["truncation"] = truncation
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:

@@ -132,8 +132,11 @@ def draw_orders(loc, orders: int, seed: int, job_id: int) -> np.ndarray:
 
 def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout: str = "off", parallel=None,
                device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None, slots_per_step: int = 1,
-               slot_policy: str = "given"):
+               slot_policy: str = "given", truncation=None):
     """Score every job along ``orders`` random visiting orders of its ``loc``.
+
+    ``truncation``: a hudiff_amd.guide.Truncation -- the scores are under the truncated sampler (model.score); a token its step's cut
+    removes scores -inf, and so do the sums it enters.  None or a neutral one passes nothing on.
 
     ``slot_policy`` = "confident" scores under the confident sampler (model.score): the order is the model's own, found teacher-forced
     from the candidate list ``loc`` as it stands (only ties ever see the list), so ``orders`` must be 1, the sequential loop runs
@@ -169,6 +172,8 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
     more = {} if int(slots_per_step) == 1 else {"slots_per_step": int(slots_per_step)}
     if confident:
         more["slot_policy"] = slot_policy
+    if truncation is not None and not truncation.neutral:
+        more["truncation"] = truncation
     from .sampler import _id_runs
     pos = np.arange(lo, hi)
     gids = jid[pos // orders] * orders + pos % orders
@@ -195,5 +200,7 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
     T = np.array([len(j.loc) for j in jobs], np.int64)
     total = logp.astype(np.float64).sum(axis=2)
     mean = total.mean(axis=1)
-    return {"total": total, "mean": mean, "std": total.std(axis=1), "per_residue": np.where(T > 0, mean / np.maximum(T, 1), 0.0),
+    with np.errstate(invalid="ignore"):              # (a -inf total -- a token the truncation removes -- has no spread: nan)
+        std = total.std(axis=1)
+    return {"total": total, "mean": mean, "std": std, "per_residue": np.where(T > 0, mean / np.maximum(T, 1), 0.0),
             "T": T, "logp": logp, "order": all_order}

@@ -60,7 +60,7 @@ extern "C" {
                                  hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
                                  hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
                                  the struct HdGuide; block decoding added hd_set_slots_per_step; the slot policy added hd_set_slot_policy and
-                                 hd_sample_order */
+                                 hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -199,7 +199,11 @@ HdStatus hd_sample_tokens(HdModel* m, int32_t* tokens);
  *     logp[b, t] = (g_s - max_j g_j) - log(sum_j exp(g_j - max_j g_j)),  j over the allowed tokens,
  * of the drawn token in a recording session and of the target in a scoring one (a target that is not allowed -> HD_ERR_INVALID at
  * hd_score_begin; so is temperature == 0).  A greedy session (temperature == 0) records the log-probability of its token under
- * the temperature-1 guided distribution. */
+ * the temperature-1 guided distribution.
+ *
+ * In a TRUNCATED session ("truncated sampling" below) logp is the log-probability under the truncated distribution (the sum runs over
+ * the kept tokens only).  A SCORING session may then return -inf: a target that the cut of its step removes has probability 0 under
+ * this sampler, logp[b, t] = -inf, the target is still written, and neither an error nor the numeric flag is raised. */
 HdStatus hd_sample_logp(HdModel* m, float* logp /* [B, Tmax] */);
 HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                         const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
@@ -311,6 +315,44 @@ HdStatus hd_set_slots_per_step(HdModel* m, int32_t k);
 enum { HD_SLOTS_GIVEN = 0, HD_SLOTS_CONFIDENT = 1 };
 HdStatus hd_set_slot_policy(HdModel* m, int32_t policy);
 HdStatus hd_sample_order(HdModel* m, int32_t* order /* [B, Tmax] */);
+
+/* ---- truncated sampling ---------------------------------------------------------------------------
+ * A session may carry a truncation (top_k, top_p, min_p): a cut of the 22-token distribution of every draw, applied in the draw stage
+ * in front of the draw.  For row b at order position t let g_j, j = 0..21, be exactly the values the draw forms without it: the raw
+ * logits in an unguided session; (z_j + bias_j) / temperature over the allowed tokens of a guided one (divisor 1 at temperature 0);
+ * -inf for a token that is not allowed.  With mx = max_j g_j:
+ *     e_j      = expf(g_j - mx) for allowed j, 0 otherwise                  (fp32, as without truncation)
+ *     esum     = sum_j e_j                                                  (the same reduction; HD_ERR_NUMERIC is still raised from THIS sum)
+ *     rank_j   = #{ i allowed : g_i > g_j  or (g_i == g_j and i < j) }      (ranking is on g, not on e: expf can merge distinct g)
+ *     before_j = sum of e_i over the i with rank_i < rank_j, accumulated in ascending token index i, fp32
+ *     keep_j   = allowed_j
+ *                and (top_k off  or rank_j < top_k)
+ *                and (top_p off  or before_j < top_p * esum)                (the smallest head whose mass reaches top_p)
+ *                and (min_p off  or e_j >= min_p)                           (e of the best token is exactly 1: p_j >= min_p * p_max)
+ *     the rank-0 token is always kept
+ *     esum'    = sum_j (keep_j ? e_j : 0)                                   (same reduction order)
+ *     p'_j     = e_j / esum' for kept j; a token that is not kept enters the argmax with -inf
+ *     token    = argmax_j p'_j / q_j        q is EXACTLY the noise position t meets without truncation (see "Noise")
+ *     logp     = (g_token - mx) - logf(esum')
+ * top_k is off when it is 0 or >= 22, top_p when it is >= 1, min_p when it is 0.  With all three off the truncation is the same as
+ * none: the library treats it as cleared and the session launches the kernels it launches without hd_set_truncation.  Valid ranges:
+ * top_k in [0, 22]; top_p finite in (0, 1]; min_p finite in [0, 1]; anything else -> HD_ERR_INVALID.
+ *
+ * Greedy (temperature 0): the token is unchanged (the argmax is always kept), no noise is read, and logp is the token's under the
+ * temperature-1 guided, truncated distribution.  Scoring: a target that is not kept gets logp[b, t] = -inf (see "likelihood scoring");
+ * this cannot be known at the begin, whose checks stay as they are.  Confident slot policy: the key becomes c_i = esum' (= 1 / max p'),
+ * formed with the same keep-set from the same forward; everything else of "slot policy", the replay property included, holds with the
+ * same truncation on both sides.  Block sessions: the truncation acts per order position, like the guide.
+ *
+ * Lifetime: as the block size and the slot policy -- one-shot: the NEXT hd_sample_begin / hd_sample / hd_score_begin / hd_score
+ * consumes it whether it succeeds or fails; hd_sample_restart and the guards' repeats keep it; hd_forward neither uses nor clears it.
+ * NULL clears a truncation not yet consumed.  Inside an open session -> HD_ERR_STATE; a NULL handle -> HD_ERR_INVALID. */
+typedef struct HdTruncation {
+    int32_t top_k;          /* keep the top_k best tokens; 0 or >= 22 = off */
+    float top_p;            /* keep the smallest head whose probability mass reaches top_p; in (0, 1], 1 = off */
+    float min_p;            /* keep tokens with p >= min_p * p_max; in [0, 1], 0 = off */
+} HdTruncation;
+HdStatus hd_set_truncation(HdModel* m, const HdTruncation* t);   /* NULL clears */
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
