@@ -19,6 +19,7 @@ HD_ACT_RELU, HD_ACT_GELU = 1, 2
 HD_DROPOUT_FAITHFUL, HD_DROPOUT_OFF, HD_DROPOUT_INJECT, HD_NO_GRAPH, HD_NO_PRUNE, HD_ONE_LANE, HD_LOOP_GRAPH = 0, 1, 2, 4, 8, 16, 32
 HD_RECORD_LOGP = 64
 HD_SLOTS_GIVEN, HD_SLOTS_CONFIDENT = 0, 1
+BEAM_MAX_WIDTH = 64
 SLOT_POLICIES = {"given": HD_SLOTS_GIVEN, "confident": HD_SLOTS_CONFIDENT}
 HD_PRECISION_DEFAULT, HD_PRECISION_F32_GEMM, HD_PRECISION_F32_ALL, HD_PRECISION_SPLIT = 0, 1, 2, 3
 PRECISIONS = {"default": HD_PRECISION_DEFAULT, "split": HD_PRECISION_SPLIT, "f32_gemm": HD_PRECISION_F32_GEMM, "f32_all": HD_PRECISION_F32_ALL}
@@ -34,6 +35,7 @@ EXPORTS = [
     "hd_sample_logp", "hd_score_begin", "hd_score", "hd_debug_launch_tally",
     "hd_set_guide", "hd_set_slots_per_step", "hd_set_slot_policy", "hd_sample_order",
     "hd_set_truncation",
+    "hd_set_beam", "hd_beam_state",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -140,6 +142,8 @@ def load():
     lib.hd_set_slot_policy.argtypes = [vp, C.c_int32]
     lib.hd_sample_order.argtypes = [vp, i32p]
     lib.hd_set_truncation.argtypes = [vp, P(HdTruncation)]
+    lib.hd_set_beam.argtypes = [vp, C.c_int32]
+    lib.hd_beam_state.argtypes = [vp, f32p, i32p, f32p]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

@@ -129,6 +129,53 @@ def apply_block_args(args, jobs, logger=None):
     return more
 
 
+def beam_arg(v):
+    w = int(v)
+    if not 1 <= w <= 64:
+        import argparse
+        raise argparse.ArgumentTypeError(f"{v}: an integer in [1, 64]")
+    return w
+
+
+def add_beam_args(p):
+    """--beam of the four samplers (beam search, include/hudiff_hip.h); without it the run is the sampling one."""
+    p.add_argument("--beam", type=beam_arg, default=0,
+                   help="beam search instead of sampling: W in [1, 64]; every input gets its W most likely, pairwise different "
+                        "humanizations under the guide and truncation flags, best first, where the replicas of a sampling run stand "
+                        "(--batch_size and --sample_number are not used; dropout is off; --logp_fpath records the scores)")
+    return p
+
+
+def parse_with_beam(p, argv):
+    """parse_args, and the combinations --beam does not take are argparse errors."""
+    args = p.parse_args(argv)
+    if args.beam:
+        if int(args.slots_per_step) > 1:
+            p.error("--beam searches one slot per forward: not together with --slots_per_step > 1")
+        if args.slot_policy != "given":
+            p.error("--beam follows the given order: not together with --slot_policy confident")
+        if float(args.temperature) == 0.0:
+            p.error("--beam ranks under a distribution: not together with --temperature 0 (the greedy decode)")
+        if getattr(args, "q_noise_fpath", None):
+            p.error("--beam reads no noise: not together with --q_noise_fpath")
+    return args
+
+
+def run_beam(model, jobs, args, kind, logger=None):
+    """The --beam run of a sampler: the guide and truncation flags applied, then sampler.beam_jobs.  -> (tokens [J, W, L], score [J, W],
+    live [J, W]) on rank 0, None elsewhere."""
+    from ..sampler import beam_jobs
+    temperature = apply_guide_args(args, kind, jobs, logger)
+    if logger is not None:
+        logger.info("Beam search: width {} (dropout off, no noise)".format(args.beam))
+    res = beam_jobs(model, jobs, args.beam, device_batch=getattr(args, "device_batch", 256), temperature=temperature,
+                    **apply_truncation_args(args, logger))
+    if res is None:
+        return None
+    tokens, score, _, live = res
+    return tokens, score, live
+
+
 def apply_guide_args(args, kind, jobs, logger=None):
     """Gives every job the guide the flags of add_guide_args describe and returns the temperature for sample_jobs[_with_retry].  No
     flag given: the jobs stay unguided.  A constraint of --constraints_fpath on a slot an input does not sample is ignored (their

@@ -19,8 +19,8 @@ from .. import dist as D
 from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
-from ..sampler import Job, noise_in_reference_order, sample_jobs_with_retry, seed_all
-from .common import (add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
+from ..sampler import Job, beam_walk, noise_in_reference_order, sample_jobs_with_retry, seed_all
+from .common import (add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
                      write_logp_csv)
 
 
@@ -56,6 +56,7 @@ def build_parser():
     add_runtime_args(p)
     add_guide_args(p)
     add_block_args(p)
+    add_beam_args(p)
     return p
 
 
@@ -81,7 +82,7 @@ def chain_is_valid(seq):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_with_beam(build_parser(), argv)
     rc = relaunch_if_asked(args, "hudiff_amd.cli.nanosample", argv)
     if rc is not None:
         return rc
@@ -124,13 +125,31 @@ def main(argv=None):
     q_noise = noise_in_reference_order(np.load(args.q_noise_fpath)["q"], jobs, args.batch_size) if args.q_noise_fpath else None
     records = [] if args.logp_fpath else None
     more = {} if records is None else {"logp_records": records}
-    temperature = apply_guide_args(args, "nb", jobs, logger)
-    if temperature != 1.0:
-        more["temperature"] = temperature
-    more.update(apply_block_args(args, jobs, logger))
-    written = sample_jobs_with_retry(model, jobs, args.batch_size, args.seed, want=args.sample_number,
-                                     tries=args.try_number, accept=lambda row: chain_is_valid(I.untokenize_nanobody(row)),
-                                     device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise, **more)
+
+    def accept(row):
+        return chain_is_valid(I.untokenize_nanobody(row))
+    if args.beam:
+        # beam search: the accept / tries walk runs once over the live rows of every input, best first, wanting all W of them (a
+        # re-sweep would return the same rows); the sidecar's logp column is the row's score
+        beam = run_beam(model, jobs, args, "nb", logger)
+        if beam is None:
+            return None
+        tokens, score, live = beam
+        written = [beam_walk(tokens[j][live[j]], args.beam, args.try_number, accept, lambda row, job=job: rejected(job, row))
+                   for j, job in enumerate(jobs)]
+        if records is not None:
+            for j, job in enumerate(jobs):
+                kept = {row.tobytes() for row in written[j]}
+                records += [(j, 0, r, len(job.loc), float(score[j, r]), int(bool(live[j, r]) and tokens[j, r].tobytes() in kept))
+                            for r in range(args.beam)]
+    else:
+        temperature = apply_guide_args(args, "nb", jobs, logger)
+        if temperature != 1.0:
+            more["temperature"] = temperature
+        more.update(apply_block_args(args, jobs, logger))
+        written = sample_jobs_with_retry(model, jobs, args.batch_size, args.seed, want=args.sample_number,
+                                         tries=args.try_number, accept=accept,
+                                         device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise, **more)
     if rank != 0:
         return None
     if records is not None:

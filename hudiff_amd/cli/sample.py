@@ -27,7 +27,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, noise_in_reference_order, sample_jobs, seed_all
-from .common import (add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
+from .common import (add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
                      write_logp_csv)
 
 
@@ -73,6 +73,7 @@ def build_parser():
     add_runtime_args(p)
     add_guide_args(p)
     add_block_args(p)
+    add_beam_args(p)
     return p
 
 
@@ -134,7 +135,7 @@ def traditional_main(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_with_beam(build_parser(), argv)
     rc = relaunch_if_asked(args, "hudiff_amd.cli.sample", argv)
     if rc is not None:
         return rc
@@ -209,7 +210,16 @@ def main(argv=None):
     # sample.py:499-538: with similarity search one pass gives the single output row; without it the loop
     # re-sweeps until sample_number rows have been written (batch_size rows per pass)
     passes = 1 if args.similarity_search else max(1, -(-args.sample_number // args.batch_size))
-    if args.sample_number <= 0 or args.try_number <= 0:            # `while sample_number > 0 and try_num > 0` never runs
+    live = None
+    if args.beam:
+        # beam search: the W best rows of every input stand where the replicas stand, best first; all live ones are written
+        beam = run_beam(model, jobs, args, "ab", logger)
+        if beam is None:
+            return None
+        args.similarity_search, args.batch_size, args.sample_number = False, args.beam, args.beam
+        result, live = beam[0][:, None], beam[2]
+        result_logp = beam[1][:, None, :, None]                        # (the sidecar's logp column is the row's score)
+    elif args.sample_number <= 0 or args.try_number <= 0:            # `while sample_number > 0 and try_num > 0` never runs
         args.sample_number = 0
         result = np.zeros((len(jobs), 0, args.batch_size, model.max_len), np.int32)
     else:
@@ -252,6 +262,8 @@ def main(argv=None):
                     for r in range(args.batch_size):
                         if left == 0:
                             break
+                        if live is not None and not live[j, r]:     # a dead beam row: fewer than W sequences exist
+                            continue
                         g_h, g_l = I.untokenize_antibody(result[j, p, r])
                         chosen.add((j, p, r))
                         f.write(f"humanization,{sample_name},{g_h},{g_l}\n")

@@ -21,7 +21,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
+from .common import add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
 
 
 def build_parser():
@@ -44,6 +44,7 @@ def build_parser():
     add_runtime_args(p)
     add_guide_args(p)
     add_block_args(p)
+    add_beam_args(p)
     return p
 
 
@@ -69,7 +70,7 @@ def variable_domain(seq, numbering):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_with_beam(build_parser(), argv)
     rc = relaunch_if_asked(args, "hudiff_amd.cli.sample_for_anti_cdr", argv)
     if rc is not None:
         return rc
@@ -104,9 +105,17 @@ def main(argv=None):
         np.random.shuffle(loc)
     job = Job(tokens=tok, region=reg, loc=loc, chain=chain, name=pdb_name)
     passes = max(0, -(-args.sample_number // args.batch_size))                 # every replica looked at counts (:212)
-    temperature = apply_guide_args(args, "ab", [job], logger)
-    result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout,
-                         **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
+    live = None
+    if args.beam:                                                              # the W best rows stand where the replicas stand
+        beam = run_beam(model, [job], args, "ab", logger)
+        if beam is None:
+            return None
+        passes, args.batch_size, args.sample_number = 1, args.beam, args.beam
+        result, live = beam[0][:, None], beam[2]
+    else:
+        temperature = apply_guide_args(args, "ab", [job], logger)
+        result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout,
+                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")
@@ -118,6 +127,8 @@ def main(argv=None):
             for r in range(args.batch_size):
                 if left == 0:
                     break
+                if live is not None and not live[0, r]:
+                    continue
                 g_h, g_l = I.untokenize_antibody(result[0, p, r])
                 if (g_h, g_l) not in seen:
                     seen.add((g_h, g_l))

@@ -22,7 +22,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_block_args, add_guide_args, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
+from .common import add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
 from .nanosample import chain_is_valid
 
 
@@ -47,6 +47,7 @@ def build_parser():
     add_runtime_args(p)
     add_guide_args(p)
     add_block_args(p)
+    add_beam_args(p)
     return p
 
 
@@ -61,7 +62,7 @@ def get_nano_seq_from_fasta(fpath):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_with_beam(build_parser(), argv)
     rc = relaunch_if_asked(args, "hudiff_amd.cli.sample_for_nano_cdr", argv)
     if rc is not None:
         return rc
@@ -89,9 +90,17 @@ def main(argv=None):
         np.random.shuffle(loc)
     passes = max(1, -(-args.sample_number // args.batch_size))
     job = Job(tokens=tok, region=reg, loc=loc, name=pdb_name)
-    temperature = apply_guide_args(args, "nb", [job], logger)
-    result = sample_jobs(model, [job], args.batch_size, args.seed, passes=passes, dropout=args.dropout,
-                         **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
+    live = None
+    if args.beam:                                                              # the W best rows stand where the replicas stand
+        beam = run_beam(model, [job], args, "nb", logger)
+        if beam is None:
+            return None
+        passes, args.batch_size, args.sample_number = 1, args.beam, args.beam
+        result, live = beam[0][:, None], beam[2]
+    else:
+        temperature = apply_guide_args(args, "nb", [job], logger)
+        result = sample_jobs(model, [job], args.batch_size, args.seed, passes=passes, dropout=args.dropout,
+                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")
@@ -103,6 +112,8 @@ def main(argv=None):
             for r in range(args.batch_size):
                 if left == 0:
                     break
+                if live is not None and not live[0, r]:
+                    continue
                 g_h = I.untokenize_nanobody(result[0, p, r])
                 if g_h not in seen:
                     if chain_is_valid(g_h):

@@ -104,6 +104,9 @@ struct Workspace {
     // what is keyed by its positions as the begin uploaded them -- slot_select_k permutes order / target / gallow / gbias in place and
     // hd_sample_restart puts them back from here.  Same capacities (capT, gbias_cap), regrown together with their originals.
     float* conf = nullptr; int32_t *order0 = nullptr, *target0 = nullptr; uint32_t* gallow0 = nullptr; float* gbias0 = nullptr;
+    // beam search (hd_set_beam): cumulative score [B], parent [B, Tmax], and the candidate table / step log-probabilities [B, 22] of the
+    // last position run.  Allocated by the first beam session of the lane and regrown like the [B, Tmax] family (a regrow drops the graphs).
+    float *bscore = nullptr, *bcand = nullptr, *blp = nullptr; int32_t* bparent = nullptr; size_t beam_capB = 0, beam_capT = 0;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -220,6 +223,7 @@ struct HdModel {
         int graph_x3 = -1;                           // kernel_set() when the graph was captured (split kernels in use, ln_sync level)
         int graph_mode = -1;                         // draw mode of the captured step (DRAW_SAMPLE / DRAW_RECORD / DRAW_SCORE)
         int graph_policy = -1;                       // slot policy of the captured step (HD_SLOTS_CONFIDENT: slot_conf_k + slot_select_k in front of the block draw)
+        int graph_W = -1;                            // beam width of the captured step (0: a draw; > 0: beam_cand_k + beam_select_k in its place)
         int graph_K = -1;                            // slots per step of the captured step (1: pruned tail + sample_step_k; > 1: full last block + sample_block_k)
         const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
         // the guide the captured draw was launched with (GUIDE_*, its temperature -- a kernel argument -- and the buffers it reads)
@@ -271,6 +275,10 @@ struct HdModel {
     TruncP trunc_next{0, 1.f, 0.f};
     bool s_trunc = false;                            // the open session truncates
     TruncP s_tr{0, 1.f, 0.f};
+    // beam search (include/hudiff_hip.h "beam search"): hd_set_beam leaves the width here; the next begin takes it like the block size
+    int beam_next = 0;
+    int sW = 0;                                      // beam width of the open (or last) session; 0 = not a beam session
+    std::vector<float> beam_score0;                  // score of every row at the begin: 0 for the first row of a group, -inf for the others
     bool order_ready = false;                        // the lanes' order buffers hold an ended session's order (hd_sample_order after the end)
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
@@ -636,6 +644,15 @@ extern "C" HdStatus hd_set_slots_per_step(HdModel* m, int32_t k) {
     if (k < 1 || k > 64) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: k = %d outside [1, 64]", k);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slots_per_step: a sampling session is open (the block size belongs to the NEXT begin)");
     m->k_next = k;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "beam search": the next begin takes it; 0 clears.
+extern "C" HdStatus hd_set_beam(HdModel* m, int32_t width) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_beam: null model");
+    if (width < 0 || width > BEAM_MAX_W) return fail(HD_ERR_INVALID, "hd_set_beam: width = %d outside [0, %d]", width, BEAM_MAX_W);
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_beam: a sampling session is open (the width belongs to the NEXT begin)");
+    m->beam_next = width;
     return HD_OK;
 }
 
@@ -1904,6 +1921,32 @@ static HdStatus slot_choose(HdModel* m, const Segs& sg) {
     return HD_OK;
 }
 
+// Candidate table and selection of a beam session, in the place of the draw: beam_cand_k on the hidden row of every row's slot (compact
+// when the tail was pruned), then beam_select_k per group, whose last workgroup advances the step.
+static HdStatus beam_step(HdModel* m, const Segs& sg, bool prune) {
+    HdModel::Lane& ln = cur(m);
+    Workspace& ws = ln.ws;
+    static_assert(BEAM_MAX_L >= 304, "beam_select_k stages whole token rows (max_len <= 304, hd_create)");
+    const float* hm = prune ? ws.Xc : ws.Y;
+    const dim3 grid(sg.B), block(64 * SS_WAVES);
+    const int compact = prune ? 1 : 0;
+    const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
+    if (m->s_trunc)
+        hipLaunchKernelGGL((beam_cand_k<true, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, compact,
+                           ws.bscore, ws.bcand, ws.blp, GuideTP{g, m->s_tr});
+    else if (m->s_guide != GUIDE_NONE)
+        hipLaunchKernelGGL(beam_cand_k<true>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, compact,
+                           ws.bscore, ws.bcand, ws.blp, g);
+    else
+        hipLaunchKernelGGL(beam_cand_k<false>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, compact,
+                           ws.bscore, ws.bcand, ws.blp, GuideP{nullptr, nullptr, 1.f});
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(beam_select_k, dim3(sg.B / m->sW), dim3(BEAM_THREADS), 0, ln.stream, ws.tokens, ws.order, ws.T, m->sTmax, m->L, m->sW, ln.rs,
+                       ws.bscore, ws.bparent, ws.logp, ws.bcand, ws.blp);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, const uint8_t* cm) {
     HdModel::Lane& ln = cur(m);
     // a block session (K > 1) visits K rows per sequence: the last attention block runs for every row, as with HD_NO_PRUNE; so does a
@@ -1912,6 +1955,7 @@ static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, 
     const bool prune = !(m->sflags & HD_NO_PRUNE) && m->sK == 1 && !confident;
     HD_TRY(forward_body(m, sg, dm, em, cm, prune));
     Workspace& ws = ln.ws;
+    if (m->sW > 0) return beam_step(m, sg, prune);   // (a beam session has K = 1 and the given order: sample_begin_impl)
     if (confident) HD_TRY(slot_choose(m, sg));
     if (m->sK > 1 || confident) return block_draw(m, sg);       // (K = 1: gridDim.y == 1, position `step`)
     // the injected Exp(1) noise lives once, for the whole batch, in the model (m->qnoise)
@@ -1961,7 +2005,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
                                   const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                   uint64_t seed, uint64_t row0, const float* q_noise,
                                   const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide, int K,
-                                  int policy, const TruncP* trunc) {
+                                  int policy, const TruncP* trunc, int W) {
     if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -1970,7 +2014,8 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     m->sB = B; m->sTmax = Tmax; m->sflags = flags; m->s_has_q = q_noise != nullptr; m->timed = false; m->last_steps = 0;
     m->s_seed = seed; m->s_steps = 0; m->s_dirty = false;
     m->nlanes = 1; m->cl = 0;
-    m->s_mode = score ? DRAW_SCORE : (flags & HD_RECORD_LOGP) ? DRAW_RECORD : DRAW_SAMPLE;
+    m->s_mode = score ? DRAW_SCORE : ((flags & HD_RECORD_LOGP) || W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
+    m->sW = 0;
     m->logp_ready = false;
     m->order_ready = false;
     m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
@@ -1982,6 +2027,19 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     HdModel::Guide neutral;
     if (trunc && !guide) { neutral.B = B; guide = &neutral; }
     const bool confident = policy == HD_SLOTS_CONFIDENT;
+    if (W > 0) {                                     // beam search: one slot per forward in the given order, no noise, no dropout
+        if (score) return fail(HD_ERR_UNSUPPORTED, "hd_score_begin: a beam width is set (hd_set_beam); a scoring session has no beam");
+        if (K > 1 || confident)
+            return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a beam session takes one slot per forward in the given order (slots per step %d%s)",
+                        K, confident ? ", confident slot policy" : "");
+        if (drop_mode_of(m, flags) != DROP_NONE)
+            return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a beam session runs with dropout off (HD_DROPOUT_OFF, or cfg.dropout == 0): generated "
+                                            "masks are keyed by row, so the rows of a group would be ranked under different sub-networks");
+        if (q_noise) return fail(HD_ERR_INVALID, "hd_sample_begin: a beam session reads no noise (q_noise must be NULL)");
+        if (guide && guide->temperature == 0.f)
+            return fail(HD_ERR_INVALID, "hd_sample_begin: a guide with temperature 0 (greedy decode) has no distribution for a beam to rank under");
+        if (B % W != 0) return fail(HD_ERR_INVALID, "hd_sample_begin: %d rows are not whole groups of beam width %d", B, W);
+    }
     if (confident && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
         return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop in the given order; a "
                                         "confident session takes generated masks or none");
@@ -1993,7 +2051,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
         if (score && guide->temperature == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
     }
-    if (B == 0) { m->sK = K; m->s_policy = policy; m->in_session = true; return HD_OK; }      // (no row: nothing to guide or truncate)
+    if (B == 0) { m->sK = K; m->s_policy = policy; m->sW = W; m->in_session = true; return HD_OK; }      // (no row: nothing to guide or truncate)
     HD_TRY(validate_inputs(m, tokens, region, chain, B));
     for (int b = 0; b < B; ++b) {
         if (T[b] < 0 || T[b] > Tmax) return fail(HD_ERR_INVALID, "T[%d] = %d out of [0,%d]", b, T[b], Tmax);
@@ -2008,6 +2066,16 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
                     if (order[(size_t)b * Tmax + u] == order[(size_t)b * Tmax + t])
                         return fail(HD_ERR_INVALID, "order[%d,%d] = order[%d,%d] = %d: a slot is repeated inside one group of %d slots per step",
                                     b, u, b, t, order[(size_t)b * Tmax + t], K);
+    }
+    // beam search: the rows of a group start as copies of its first row (only that row is live; the others are filled by the gather)
+    for (int b = 0; W > 0 && b < B; ++b) {
+        const int a = b / W * W;
+        if (a == b) continue;
+        bool same = T[b] == T[a] && memcmp(tokens + (size_t)b * m->L, tokens + (size_t)a * m->L, (size_t)m->L * sizeof(int32_t)) == 0 &&
+                    memcmp(region + (size_t)b * m->L, region + (size_t)a * m->L, (size_t)m->L * sizeof(int32_t)) == 0;
+        if (same && T[b] > 0) same = memcmp(order + (size_t)b * Tmax, order + (size_t)a * Tmax, (size_t)T[b] * sizeof(int32_t)) == 0;
+        if (same && m->nseg > 1) same = chain[b] == chain[a] && chain[B + b] == chain[B + a];
+        if (!same) return fail(HD_ERR_INVALID, "hd_sample_begin: row %d differs from row %d, the first of its beam group (tokens, region, chain, order and T must be equal)", b, a);
     }
     // slot policy: the candidate list of a confident session is a set -- any of its slots may meet any other in one group
     if (confident) {
@@ -2064,12 +2132,18 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     // or the caller asked for one lane
     const long lane_min_b = m->opt[HD_OPT_LANE_MIN_ROWS];
     m->nlanes = (B >= lane_min_b && dm != DROP_INJECT && !(flags & HD_ONE_LANE)) ? (int)m->opt[HD_OPT_LANES] : 1;
-    if (m->nlanes > B) m->nlanes = B;
+    const int unit = W > 0 ? W : 1, nunit = B / unit;  // a beam session is cut at group boundaries
+    if (m->nlanes > nunit) m->nlanes = nunit;
     for (int l = 0, off = 0; l < m->nlanes; ++l) {            // balanced contiguous row blocks
-        const int Bl = B / m->nlanes + (l < B % m->nlanes ? 1 : 0);
+        const int Bl = unit * (nunit / m->nlanes + (l < nunit % m->nlanes ? 1 : 0));
         m->lane[l].B = Bl; m->lane[l].row_off = off;
         off += Bl;
     }
+    if (W > 0) {
+        m->beam_score0.assign((size_t)B, -INFINITY);
+        for (int b = 0; b < B; b += W) m->beam_score0[b] = 0.f;
+    }
+    const auto need_T = [](int Bl, int Tm) { return (size_t)Bl * (Tm > 0 ? Tm : 1); };
     std::vector<int32_t> chain_l;
     for (int l = 0; l < m->nlanes; ++l) {
         m->cl = l;
@@ -2128,6 +2202,27 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
                 ws.gbias_cap = need * 22;
             }
         }
+        if (W > 0) {
+            if ((size_t)Bl > ws.beam_capB || need_T(Bl, Tmax) > ws.beam_capT) {
+                HIP_TRY(hipStreamSynchronize(ln.stream));
+                for (void* old : {(void*)ws.bscore, (void*)ws.bcand, (void*)ws.blp, (void*)ws.bparent}) {
+                    if (!old) continue;
+                    for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
+                        if (*it == old) { ws.owned.erase(it); break; }
+                    hipFree(old);
+                }
+                ws.bscore = nullptr; ws.bcand = nullptr; ws.blp = nullptr; ws.bparent = nullptr; ws.beam_capB = 0; ws.beam_capT = 0;
+                ln.drop_graphs();                    // a captured beam step holds the old pointers
+                HD_TRY(dalloc(ws, &ws.bscore, (size_t)Bl));
+                HD_TRY(dalloc(ws, &ws.bcand, (size_t)Bl * 22));
+                HD_TRY(dalloc(ws, &ws.blp, (size_t)Bl * 22));
+                HD_TRY(dalloc(ws, &ws.bparent, need_T(Bl, Tmax)));
+                ws.beam_capB = (size_t)Bl; ws.beam_capT = need_T(Bl, Tmax);
+            }
+            HIP_TRY(hipMemcpyAsync(ws.bscore, m->beam_score0.data() + off, (size_t)Bl * sizeof(float), hipMemcpyHostToDevice, ln.stream));
+            HIP_TRY(hipMemsetAsync(ws.bparent, 0, need_T(Bl, Tmax) * sizeof(int32_t), ln.stream));
+            HIP_TRY(hipMemsetAsync(ws.bcand, 0, (size_t)Bl * 22 * sizeof(float), ln.stream));
+        }
         if (guide && Tmax > 0) {
             HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
             if (guide->has_bias)
@@ -2173,6 +2268,7 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     if (guide) { m->s_guide = guide->has_bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW; m->s_temp = guide->temperature; }
     m->sK = K;
     m->s_policy = policy;
+    m->sW = W;
     if (trunc) { m->s_trunc = true; m->s_tr = *trunc; }
     m->in_session = true;
     return HD_OK;
@@ -2203,6 +2299,14 @@ static int take_slot_policy(HdModel* m) {
     return p;
 }
 
+// And the beam width hd_set_beam left.
+static int take_beam(HdModel* m) {
+    if (!m) return 0;
+    const int w = m->beam_next;
+    m->beam_next = 0;
+    return w;
+}
+
 // And the truncation hd_set_truncation left.
 static bool take_truncation(HdModel* m, TruncP* tr) {
     if (!m || !m->trunc_pending) return false;
@@ -2223,12 +2327,14 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
     const int policy = take_slot_policy(m);
     TruncP tr;
     const bool truncated = take_truncation(m, &tr);
+    const int W = take_beam(m);
     const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K, policy,
-                                         truncated ? &tr : nullptr);
+                                         truncated ? &tr : nullptr, W);
     if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
         m->s_policy = HD_SLOTS_GIVEN;
         m->s_trunc = false;
+        m->sW = 0;
     }
     return s;
 }
@@ -2245,12 +2351,14 @@ extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int3
     const int policy = take_slot_policy(m);
     TruncP tr;
     const bool truncated = take_truncation(m, &tr);
+    const int W = take_beam(m);
     const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K, policy,
-                                         truncated ? &tr : nullptr);
+                                         truncated ? &tr : nullptr, W);
     if (s != HD_OK && m && !was_open) {
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
         m->s_policy = HD_SLOTS_GIVEN;
         m->s_trunc = false;
+        m->sW = 0;
     }
     return s;
 }
@@ -2268,6 +2376,10 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (m->s_mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
+        if (m->sW > 0) {                             // beam search: only the first row of every group is live again
+            HIP_TRY(hipMemcpyAsync(ln.ws.bscore, m->beam_score0.data() + ln.row_off, (size_t)ln.B * sizeof(float), hipMemcpyHostToDevice, ln.stream));
+            HIP_TRY(hipMemsetAsync(ln.ws.bparent, 0, (size_t)ln.B * (m->sTmax > 0 ? m->sTmax : 1) * sizeof(int32_t), ln.stream));
+        }
         if (m->s_policy == HD_SLOTS_CONFIDENT && m->sTmax > 0) {      // back to the caller's candidate list
             const size_t nT = (size_t)ln.B * m->sTmax;
             HIP_TRY(hipMemcpyAsync(ln.ws.order, ln.ws.order0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
@@ -2303,7 +2415,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         const uint32_t gflags = m->sflags & HD_NO_PRUNE;
         if (!ln.graph_exec || ln.graph_B != ln.B || ln.graph_flags != gflags || ln.graph_drop != dm || ln.graph_q != m->s_has_q ||
             ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
-            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K || ln.graph_policy != m->s_policy ||
+            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K || ln.graph_policy != m->s_policy || ln.graph_W != m->sW ||
             ln.graph_guide != m->s_guide || (m->s_guide != GUIDE_NONE && (ln.graph_temp != m->s_temp || ln.graph_gallow != ln.ws.gallow)) ||
             (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias) || ln.graph_trunc != m->s_trunc ||
             (m->s_trunc && (ln.graph_tr.top_k != m->s_tr.top_k || ln.graph_tr.top_p != m->s_tr.top_p || ln.graph_tr.min_p != m->s_tr.min_p))) {
@@ -2317,7 +2429,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             HIP_TRY(hipGraphInstantiate(&ln.graph_exec, ln.graph, nullptr, nullptr, 0));
             ln.graph_B = ln.B; ln.graph_flags = gflags; ln.graph_drop = dm; ln.graph_q = m->s_has_q; ln.graph_Tmax = m->sTmax;
             ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
-            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K; ln.graph_policy = m->s_policy;
+            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K; ln.graph_policy = m->s_policy; ln.graph_W = m->sW;
             ln.graph_guide = m->s_guide; ln.graph_temp = m->s_temp; ln.graph_gallow = ln.ws.gallow; ln.graph_gbias = ln.ws.gbias;
             ln.graph_trunc = m->s_trunc; ln.graph_tr = m->s_tr;
         }
@@ -2527,6 +2639,30 @@ extern "C" HdStatus hd_sample_logp(HdModel* m, float* logp) {
         if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
         else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
         if (m->s_dirty) return fail(HD_ERR_STATE, "hd_sample_logp: a guard of the split-precision kernels fired during these steps; their values "
+                                                   "are invalid (hd_sample_end repeats the sample)");
+    } else {
+        for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+    }
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "beam search": score, parent and the candidate table of the last position run.
+extern "C" HdStatus hd_beam_state(HdModel* m, float* score, int32_t* parent, float* cand) {
+    if (!m || (!m->in_session && !m->logp_ready)) return fail(HD_ERR_STATE, "hd_beam_state: no beam session (open, or ended and not yet replaced)");
+    if (m->sW <= 0) return fail(HD_ERR_STATE, "hd_beam_state: the session is not a beam session (hd_set_beam)");
+    if (m->sB == 0) return HD_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        if (score) HIP_TRY(hipMemcpyAsync(score + ln.row_off, ln.ws.bscore, (size_t)ln.B * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
+        if (parent && m->sTmax > 0)
+            HIP_TRY(hipMemcpyAsync(parent + (size_t)ln.row_off * m->sTmax, ln.ws.bparent, (size_t)ln.B * m->sTmax * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+        if (cand) HIP_TRY(hipMemcpyAsync(cand + (size_t)ln.row_off * 22, ln.ws.bcand, (size_t)ln.B * 22 * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
+    }
+    if (m->in_session) {
+        if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
+        else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+        if (m->s_dirty) return fail(HD_ERR_STATE, "hd_beam_state: a guard of the split-precision kernels fired during these steps; their values "
                                                    "are invalid (hd_sample_end repeats the sample)");
     } else {
         for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));

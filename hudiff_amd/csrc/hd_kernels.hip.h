@@ -2525,12 +2525,15 @@ __device__ __forceinline__ bool trunc_keep(float g, float e, bool allowed, float
     return keep || (allowed && rank == 0);
 }
 
-template <int NW, int MODE = DRAW_SAMPLE, bool GUIDED = false, bool TRUNC = false>
-__device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w, int32_t* __restrict__ tokens, int b, int slot, uint32_t t,
-                                           const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
-                                           float* lg, float* __restrict__ logp_out = nullptr, int target = 0,
-                                           const uint32_t* __restrict__ g_allow = nullptr, const float* __restrict__ g_bias = nullptr,
-                                           float g_temp = 1.f, [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
+// The distribution of one (row, order position) as the draw stage forms it -- shared by the draw (sample_row) and by the candidate table
+// of a beam session (beam_cand_k), so that both hold the same bits.  Called by every wave of the block; false for the waves that are
+// done (all but wave 0).  Wave 0, lane j < 22 = token j: g (the guided logit, -inf when not allowed), mx = max g, e = expf(g - mx),
+// esum = the sum over the kept tokens (the numeric flag is raised from the full one), allowed / kept / greedy as sample_row uses them.
+struct DrawDist { float g, mx, e, esum; bool allowed, kept, greedy; };
+template <int NW, bool GUIDED, bool TRUNC>
+__device__ __forceinline__ bool draw_dist(const float* x, int D, const HeadW& w, const RunState* __restrict__ rs, float* lg,
+                                          const uint32_t* __restrict__ g_allow, const float* __restrict__ g_bias, float g_temp,
+                                          [[maybe_unused]] const TruncP& tr, DrawDist& d) {
     static_assert(GUIDED || !TRUNC, "a truncated session runs the guided form");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the guide of this (row, step): asked for before the decoder's dot products, used behind them (wave 0, lane j = token j)
@@ -2556,7 +2559,7 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
         }
     }
     __syncthreads();
-    if (wave != 0) return;
+    if (wave != 0) return false;
     float mylogit = lane < 22 ? lg[lane] : -INFINITY;
     [[maybe_unused]] bool greedy = false;
     if constexpr (GUIDED) {
@@ -2580,6 +2583,21 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
         kept = trunc_keep(mylogit, e, allowed, esum, lane, tr);
         esum = wave_sum(kept ? e : 0.f);
     }
+    d.g = mylogit; d.mx = mx; d.e = e; d.esum = esum; d.allowed = allowed; d.kept = kept; d.greedy = greedy;
+    return true;
+}
+
+template <int NW, int MODE = DRAW_SAMPLE, bool GUIDED = false, bool TRUNC = false>
+__device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w, int32_t* __restrict__ tokens, int b, int slot, uint32_t t,
+                                           const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
+                                           float* lg, float* __restrict__ logp_out = nullptr, int target = 0,
+                                           const uint32_t* __restrict__ g_allow = nullptr, const float* __restrict__ g_bias = nullptr,
+                                           float g_temp = 1.f, [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
+    const int lane = threadIdx.x & 63;
+    DrawDist d;
+    if (!draw_dist<NW, GUIDED, TRUNC>(x, D, w, rs, lg, g_allow, g_bias, g_temp, tr, d)) return;
+    const float mylogit = d.g, mx = d.mx, e = d.e, esum = d.esum;
+    [[maybe_unused]] const bool allowed = d.allowed, kept = d.kept, greedy = d.greedy;
     if constexpr (MODE == DRAW_SCORE) {
         const float zt = __shfl(mylogit, target & 31);
         [[maybe_unused]] int kt = 1;
@@ -2910,6 +2928,102 @@ __global__ void __launch_bounds__(SEL_THREADS) slot_select_k(int32_t* __restrict
         if (gbias) {
 #pragma unroll
             for (int j = 0; j < 22; ++j) gbias[(p0 + dst) * 22 + j] = gb[j];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Beam search (hd_set_beam, include/hudiff_hip.h "beam search"): two launches take the place of the draw of a one-slot step.  A lane
+// holds whole groups of W consecutive rows; the rows of a group share order, T and everything but their tokens.
+//
+// beam_cand_k: one workgroup per row, the front half of the draw (draw_dist: the same normalisation, dot products, guide and keep-set,
+// so lp has the bits a recording draw would store).  lp[b, j] = (g_j - mx) - logf(esum') for a kept token, -inf otherwise;
+// cand[b, j] = score[b] + lp[b, j].  Does not advance rs->step.
+// ------------------------------------------------------------------------------------------------
+template <bool GUIDED, bool TRUNC = false>
+__global__ void __launch_bounds__(64 * SS_WAVES) beam_cand_k(const float* __restrict__ Hm, int D, HeadW w,
+                                                   const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
+                                                   const RunState* __restrict__ rs, Segs sg, int compact,
+                                                   const float* __restrict__ score, float* __restrict__ cand, float* __restrict__ lp,
+                                                   [[maybe_unused]] GuideArg<TRUNC> ga) {
+    __shared__ float lg[32];
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((int)t >= T[b]) return;                          // (the whole workgroup)
+    const long bt = (long)b * Tmax + t;
+    const int slot = order[bt];
+    const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
+    DrawDist d;
+    bool wave0;
+    if constexpr (GUIDED) {
+        GuideP g;
+        TruncP tr{0, 1.f, 0.f};
+        if constexpr (TRUNC) { g = ga.g; tr = ga.tr; } else g = ga;
+        wave0 = draw_dist<SS_WAVES, true, TRUNC>(x, D, w, rs, lg, g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr, d);
+    } else {
+        wave0 = draw_dist<SS_WAVES, false, false>(x, D, w, rs, lg, nullptr, nullptr, 1.f, TruncP{0, 1.f, 0.f}, d);
+    }
+    if (!wave0 || lane >= 22) return;
+    const float v = (d.allowed && d.kept) ? (d.g - d.mx) - logf(d.esum) : -INFINITY;
+    lp[(long)b * 22 + lane] = v;
+    cand[(long)b * 22 + lane] = score[b] + v;
+}
+
+// beam_select_k: one workgroup per group.  The W * 22 candidates (w, j) go to LDS; a candidate that is -inf or NaN gets the key -inf, so
+// that it ranks behind every finite one and, among its like, in (w, j) order.  Every thread counts, for its candidates, the candidates
+// ahead of them (larger key, or the same key and a smaller index) -- its rank in the total order; the counting stops at W, nobody needs
+// more.  Rank r < W becomes row r of the group: the token rows of the group are staged in LDS as bytes before any is overwritten, then
+// row r is its parent's row with tokens[slot] = j, score = cand, parent[b, t] = w, logp[b, t] = lp[w, j].  No atomics on floats: the
+// result is a function of the table alone.  The last workgroup moves rs->step on, as the draw does.
+constexpr int BEAM_MAX_W = 64, BEAM_THREADS = 256, BEAM_MAX_L = 304;
+constexpr int BEAM_LDS = BEAM_MAX_W * 22 * 4 + BEAM_MAX_W * BEAM_MAX_L + BEAM_MAX_W * 4;
+static_assert(lds_fill_ok(BEAM_LDS, BEAM_THREADS), "beam_select_k: LDS co-residency rule");
+__global__ void __launch_bounds__(BEAM_THREADS) beam_select_k(int32_t* __restrict__ tokens, const int32_t* __restrict__ order,
+                                                    const int32_t* __restrict__ T, int Tmax, int L, int W, RunState* __restrict__ rs,
+                                                    float* __restrict__ score, int32_t* __restrict__ parent, float* __restrict__ logp,
+                                                    const float* __restrict__ cand, const float* __restrict__ lp) {
+    __shared__ float key[BEAM_MAX_W * 22];
+    __shared__ uint8_t stage[BEAM_MAX_W * BEAM_MAX_L];
+    __shared__ int sel[BEAM_MAX_W];
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * W;                       // first row of the group
+    const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int N = W * 22;
+    if ((int)t < T[b0] && W <= BEAM_MAX_W && L <= BEAM_MAX_L) {      // (uniform over the workgroup; the begin has checked W and L)
+        const int slot = order[(long)b0 * Tmax + t];
+        for (int i = tid; i < N; i += BEAM_THREADS) {
+            const float c = cand[(long)b0 * 22 + i];
+            key[i] = c > -INFINITY ? c : -INFINITY;      // (NaN compares false)
+        }
+        for (int i = tid; i < W * L; i += BEAM_THREADS) stage[i] = (uint8_t)tokens[(long)b0 * L + i];
+        __syncthreads();
+        for (int i = tid; i < N; i += BEAM_THREADS) {
+            const float c = key[i];
+            int r = 0;
+            for (int u0 = 0; u0 < N && r < W; u0 += 22)
+                for (int u = u0; u < u0 + 22; ++u) { const float cu = key[u]; r += (cu > c || (cu == c && u < i)) ? 1 : 0; }
+            if (r < W) sel[r] = i;
+        }
+        __syncthreads();
+        for (int i = tid; i < W * L; i += BEAM_THREADS) {
+            const int r = i / L, l = i - r * L;
+            const int s = sel[r], pw = s / 22;
+            tokens[(long)b0 * L + i] = l == slot ? s - pw * 22 : (int32_t)stage[pw * L + l];
+        }
+        if (tid < W) {
+            const int s = sel[tid], pw = s / 22;
+            const long bt = (long)(b0 + tid) * Tmax + t;
+            score[b0 + tid] = cand[(long)b0 * 22 + s];
+            parent[bt] = pw;
+            logp[bt] = lp[(long)b0 * 22 + s];
+        }
+    }
+    __syncthreads();                                     // every wave has read the step before thread 0 goes on
+    if (tid == 0) {
+        __threadfence();
+        if (atomicAdd(&rs->done, 1u) == gridDim.x - 1) {
+            __hip_atomic_store(&rs->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&rs->step, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }

@@ -195,6 +195,53 @@ def confidence_keys(logits, allow=None, bias=None, temperature=1.0, truncation=N
         return np.where(good, np.log(np.where(good, c, 1.0)), np.inf)
 
 
+def beam_select(cand, width):
+    """Step 3 of include/hudiff_hip.h "beam search" in numpy: cand float32 [W, 22] is the candidate table of one group,
+    cand[w, j] = score[w] + lp[w, j].  The candidates (w, j) are ranked by cand descending, ties to the smaller (w, j) compared
+    lexicographically; a candidate that is -inf or NaN ranks behind every finite one, in (w, j) order among its like.  Returns
+    ``(w, j, value)``: int64 [width], int64 [width], float32 [width] -- row r of the group becomes candidate (w[r], j[r]) and takes
+    value[r] = cand[w[r], j[r]] (as it stands in the table) for its score."""
+    cand = np.asarray(cand, np.float32)
+    if cand.ndim != 2 or cand.shape[1] != N_DRAW:
+        raise ValueError(f"cand must be [W, {N_DRAW}], got {cand.shape}")
+    width = int(width)
+    if not 1 <= width <= cand.size:
+        raise ValueError(f"width must be in [1, {cand.size}], got {width}")
+    flat = cand.reshape(-1)
+    key = np.where(flat > -np.inf, flat, -np.inf)    # (NaN compares false)
+    order = np.argsort(-key, kind="stable")[:width]  # a stable sort keeps (w, j) order among equal keys
+    return order // N_DRAW, order % N_DRAW, flat[order]
+
+
+def beam_backtrack(tokens, score, parent, logp, T, width):
+    """Host side of a finished beam session: tokens [G*W, L], score [G*W], parent [G*W, Tmax] (index inside the group of the row that
+    row b continued at position t), the raw step values logp [G*W, Tmax] and T [G] (positions of each group) -> (tokens [G, W, L], score [G, W], logp [G, W, Tmax],
+    live [G, W]).  Final row (g, r) reads its history by following parent backwards from position T[g] - 1 (positions t >= T[g] were never run: their
+    history is 0); live = finite score."""
+    tokens, score = np.asarray(tokens), np.asarray(score, np.float32)
+    parent, logp = np.asarray(parent), np.asarray(logp, np.float32)
+    W = int(width)
+    B = tokens.shape[0]
+    if W < 1 or B % W != 0:
+        raise ValueError(f"{B} rows are not whole groups of width {W}")
+    G, Tmax = B // W, parent.shape[1]
+    if score.shape != (B,) or parent.shape != (B, Tmax) or logp.shape != (B, Tmax):
+        raise ValueError(f"score / parent / logp must be [{B}], [{B}, Tmax], [{B}, Tmax]; got {score.shape}, {parent.shape}, {logp.shape}")
+    if parent.size and (parent.min() < 0 or parent.max() >= W):
+        raise ValueError(f"parent indices must be in [0, {W})")
+    T = np.asarray(T).reshape(-1)
+    if T.shape != (G,):
+        raise ValueError(f"T must be [{G}] (one entry per group), got {T.shape}")
+    hist = np.zeros((G, W, Tmax), np.float32)
+    base = (np.arange(G) * W)[:, None]
+    cur = np.broadcast_to(np.arange(W), (G, W)).copy()           # the row (inside its group) whose step value position t reads
+    for t in range(Tmax - 1, -1, -1):
+        rows, run = base + cur, (t < T)[:, None]
+        hist[:, :, t] = np.where(run, logp[rows, t], 0.0)
+        cur = np.where(run, parent[rows, t], cur)
+    return tokens.reshape(G, W, -1), score.reshape(G, W), hist, np.isfinite(score).reshape(G, W)
+
+
 def parse_constraints(lines, kind):
     """Text constraints -> allow uint32 [L] (L = 291 for kind 'ab', 152 for 'nb').
 

@@ -379,6 +379,87 @@ class _Denoiser:
         L.check(self._lib.hd_sample_logp(self._h, L.ptr(logp, C.c_float)))
         return logp
 
+    # -- beam search -------------------------------------------------------------------------------
+    def set_beam(self, width):
+        """hd_set_beam: the beam width W in [1, 64] (0 clears) of the NEXT sample / sample_begin on this handle, which consumes it
+        whether it succeeds or fails (include/hudiff_hip.h "beam search")."""
+        L.check(self._lib.hd_set_beam(self._h, int(width)))
+
+    def beam_state(self, B=None, Tmax=None):
+        """hd_beam_state: (score float32 [B], parent int32 [B, Tmax], cand float32 [B, 22]) of the open beam session, or of the last
+        one; cand is the candidate table of the last position run."""
+        B = self._session_B if B is None else B
+        Tmax = self._session_Tmax if Tmax is None else Tmax
+        score = np.zeros(B, dtype=np.float32)
+        parent = np.zeros((B, Tmax), dtype=np.int32)
+        cand = np.zeros((B, 22), dtype=np.float32)
+        L.check(self._lib.hd_beam_state(self._h, L.ptr(score, C.c_float), L.ptr(parent, C.c_int32), L.ptr(cand, C.c_float)))
+        return score, parent, cand
+
+    def beam_begin(self, tokens, region, chain, order, T, width, *, guide=None, truncation=None, dropout="off", graph=True, prune=True,
+                   lanes=2, seed=0, row0=0):
+        """hd_set_beam + hd_sample_begin: a beam session of width W on rows that are ALREADY replicated -- tokens [G*W, L], every row
+        of a group equal to its first.  sample_run / sample_restart / sync / sample_tokens / sample_logp / beam_state / sample_end
+        work on it; it always records."""
+        tok, reg, chn, order, T, B, Tmax, _, _, _, _ = self._sample_args(tokens, region, chain, order, T, None, None, None)
+        self.set_beam(width)
+        try:
+            self._arm(guide, B, 1, "given", truncation)
+        except Exception:
+            self._lib.hd_set_beam(self._h, 0)        # (no begin will follow to consume it)
+            raise
+        L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
+                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
+                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0), None, None, None))
+        self._session_B, self._session_Tmax = B, Tmax
+
+    def beam_search(self, tokens, region, chain, order, T, width, *, guide=None, truncation=None, lanes=2, graph=True):
+        """The W most likely, pairwise different completions of every row along its visiting order, ranked: tokens [G, L], order
+        [G, Tmax], T [G] as for ``sample``; ``width`` = W in [1, 64].  Each row is replicated W times, a [G, ...] guide is expanded to
+        [G*W, ...], the session runs on the device (include/hudiff_hip.h "beam search": dropout off, no noise) and ``parent`` is
+        followed backwards on the host.  Returns numpy arrays
+            tokens [G, W, L]     the final rows of every group, best first
+            score  [G, W]        their cumulative log-probability (-inf for a dead row: fewer than W sequences exist)
+            logp   [G, W, Tmax]  the step values along each final row's own history, aligned to order positions
+            live   [G, W]        score is finite."""
+        from .guide import beam_backtrack
+        W = int(width)
+        if isinstance(width, (bool, float)) or W != width or not 1 <= W <= L.BEAM_MAX_WIDTH:
+            raise ValueError(f"width must be an integer in [1, {L.BEAM_MAX_WIDTH}], got {width!r}")
+        tok, _ = _to_numpy(tokens)
+        reg, _ = _to_numpy(region)
+        chn, _ = _to_numpy(chain)
+        tok, reg, order, T = np.asarray(tok), np.asarray(reg), np.asarray(order), np.asarray(T).reshape(-1)
+        if tok.ndim != 2 or tok.shape[1] != self.max_len:
+            raise ValueError(f"tokens must be [G, {self.max_len}], got {tok.shape}")
+        G = tok.shape[0]
+        if reg.shape != tok.shape or order.ndim != 2 or order.shape[0] != G or T.shape != (G,):
+            raise ValueError(f"region must be {tok.shape}, order [{G}, Tmax] and T [{G}]; got {reg.shape}, {order.shape}, {T.shape}")
+        rep = np.repeat(np.arange(G), W)
+        if self.kind == "ab":
+            if chn is None:
+                raise ValueError("AntiTFNet needs H_L_chn_type [2G]")
+            chn = np.asarray(chn).reshape(-1)
+            if chn.shape != (2 * G,):
+                raise ValueError(f"chain must be [{2 * G}], got {chn.shape}")
+            chn = np.concatenate([chn[:G][rep], chn[G:][rep]])
+        else:
+            chn = None
+        if guide is not None:
+            guide.batch(G, self.max_len)             # (shape check against the groups as given)
+            guide = guide.take(rep)
+        self.beam_begin(tok[rep], reg[rep], chn, order[rep], T[rep], W, guide=guide, truncation=truncation, lanes=lanes, graph=graph)
+        Tmax = order.shape[1]
+        if G and Tmax:
+            try:
+                self.sample_run(0, Tmax)
+            except Exception:
+                self._lib.hd_sample_end(self._h, None)       # (closes the session; the error of the run is the one that travels)
+                raise
+        out = self.sample_end()
+        score, parent, _ = self.beam_state(G * W, Tmax)
+        return beam_backtrack(out, score, parent, self.sample_logp(G * W, Tmax), T, W)
+
     # -- likelihood of given sequences -------------------------------------------------------------
     def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given",
                    truncation=None):

@@ -139,6 +139,79 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     return res if len(res) > 1 else tokens
 
 
+def beam_jobs(model, jobs: Sequence[Job], width: int, *, device_batch: int = 256, all_ranks: bool = False, temperature: float = 1.0,
+              truncation=None):
+    """Beam search (model.beam_search) of width W over every job: the W most likely, pairwise different completions of each along its
+    ``loc``, ranked.  A launch takes floor(device_batch / W) jobs (at least one); jobs are sharded over ranks and gathered like tokens.
+    Returns, on rank 0 (every rank when single-process or ``all_ranks``; None elsewhere),
+        tokens int32 [len(jobs), W, L], score float32 [len(jobs), W], logp float32 [len(jobs), W, Tmax], live bool [len(jobs), W]
+    as model.beam_search returns them.  ``temperature`` and the jobs' ``guide`` fields, and ``truncation``, shape the distribution the
+    beam ranks under, as in ``sample_jobs``; temperature 0 has no distribution and is an error.  A job with replica states
+    (tokens [replicas, L]) is not a beam input."""
+    W = int(width)
+    if float(temperature) == 0.0:
+        raise ValueError("beam search ranks under a distribution: temperature 0 (the greedy decode) has none")
+    if any(np.ndim(j.tokens) != 1 for j in jobs):
+        raise ValueError("beam search takes one state per job (tokens [L])")
+    guided = float(temperature) != 1.0 or any(j.guide is not None for j in jobs)
+    L = model.max_len
+    rank, world, _ = D.env_rank_world()
+    lo, hi = D.shard_bounds(len(jobs), rank, world)
+    is_ab = model.kind == "ab"
+    Tmax = max([len(j.loc) for j in jobs] + [1])
+    tok = np.zeros((hi - lo, W, L), np.int32)
+    score = np.full((hi - lo, W), -np.inf, np.float32)
+    lp = np.zeros((hi - lo, W, Tmax), np.float32)
+    per = max(1, int(device_batch) // max(W, 1))
+    for s in range(lo, hi, per):
+        jb = list(jobs[s:min(hi, s + per)])
+        order = np.zeros((len(jb), Tmax), np.int32)
+        T = np.zeros(len(jb), np.int32)
+        for r, j in enumerate(jb):
+            order[r, :len(j.loc)] = j.loc
+            T[r] = len(j.loc)
+        chain = np.array([j.chain[0] for j in jb] + [j.chain[1] for j in jb], np.int32) if is_ab else None
+        more = {}
+        if guided:
+            from .guide import Guide
+            more["guide"] = Guide.stack([j.guide for j in jb], L, temperature)
+        if truncation is not None and not truncation.neutral:
+            more["truncation"] = truncation
+        e = s - lo + len(jb)
+        tok[s - lo:e], score[s - lo:e], lp[s - lo:e], _ = model.beam_search(
+            np.stack([j.tokens for j in jb]).astype(np.int32), np.stack([j.region for j in jb]).astype(np.int32), chain, order, T, W, **more)
+    # one row per job through the gather of the tokens (the float32 bits travel as int32)
+    n = len(jobs)
+    g_tok = D.gather_rows(tok.reshape(hi - lo, W * L), n, W * L, all_ranks)
+    g_score = D.gather_rows(score.view(np.int32), n, W, all_ranks)
+    g_lp = D.gather_rows(lp.reshape(hi - lo, W * Tmax).view(np.int32), n, W * Tmax, all_ranks)
+    if g_tok is None:
+        return None
+    score = np.ascontiguousarray(g_score, dtype=np.int32).view(np.float32).reshape(n, W)
+    logp = np.ascontiguousarray(g_lp, dtype=np.int32).view(np.float32).reshape(n, W, Tmax)
+    return g_tok.reshape(n, W, L), score, logp, np.isfinite(score)
+
+
+def beam_walk(rows, want: int, tries: int, accept, log=None):
+    """One accept / tries walk of sample_jobs_with_retry over the rows of a beam, best first (a re-sweep would return the same rows):
+    stop when nothing is wanted; an accepted row is written and counted; a rejected row is written only when ``tries == 1``;
+    ``tries`` drops by one per row looked at.  Returns the rows written, in order."""
+    out, left = [], want
+    for row in rows:
+        if left == 0:
+            break
+        if accept(row):
+            out.append(row)
+            left -= 1
+        else:
+            if tries == 1:
+                out.append(row)
+            if log is not None:
+                log(row)
+        tries -= 1
+    return out
+
+
 def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.ndarray:
     """Recorded ``torch.multinomial`` noise of a REFERENCE run -> the ``q_noise`` argument of ``sample_jobs``.
 

@@ -60,7 +60,8 @@ extern "C" {
                                  hd_set_option, hd_get_option, hd_debug_scatter_lnsync), likelihood scoring added hd_sample_logp, hd_score_begin,
                                  hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
                                  the struct HdGuide; block decoding added hd_set_slots_per_step; the slot policy added hd_set_slot_policy and
-                                 hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation */
+                                 hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation; beam search added hd_set_beam and
+                                 hd_beam_state */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -353,6 +354,47 @@ typedef struct HdTruncation {
     float min_p;            /* keep tokens with p >= min_p * p_max; in [0, 1], 0 = off */
 } HdTruncation;
 HdStatus hd_set_truncation(HdModel* m, const HdTruncation* t);   /* NULL clears */
+
+/* ---- beam search ----------------------------------------------------------------------------------
+ * A session may carry a beam width W in [1, 64]: it is then a SEARCH, not a sampler.  Its B = G * W rows are G groups of W consecutive
+ * rows (rows g*W .. g*W+W-1 are group g), and the device keeps, position by position, the W best continuations of every group.
+ * State per row: score[b] (fp32, the cumulative log-probability) and parent[b, t] (int32).  At the begin and at hd_sample_restart
+ * score is 0 for the first row of each group and -inf ("dead") for the others; parent is 0.
+ *
+ * Order position t of group g, for t < T (a group with t >= T is left untouched):
+ *   1. one denoiser forward, as in a one-slot session (the pruned tail applies: every row visits order[b, t]);
+ *   2. candidates: for every row b of the group g_j, mx, e_j, esum, the keep-set and esum' are formed exactly as the draw stage forms
+ *      them for an unguided, guided or truncated session (same arithmetic, same reduction order; HD_ERR_NUMERIC from the full sum), then
+ *          lp[b, j]   = (g_j - mx) - logf(esum')   for a kept token, -inf for a token that is not allowed or not kept
+ *          cand[b, j] = score[b] + lp[b, j]        (one fp32 add)
+ *   3. selection: the W * 22 candidates (w, j) of the group are ranked by cand descending; ties go to the smaller (w, j), compared
+ *      lexicographically; a candidate that is -inf or NaN ranks behind every finite one, in (w, j) order among its like;
+ *   4. gather: the candidate of rank r < W becomes row g*W + r: its tokens are the parent row's with tokens[order[t]] = j,
+ *      score = cand, parent[b, t] = w (the index inside the group), logp[b, t] = lp[w, j].
+ * Rows therefore always stand in score order.  A dead row stays well formed: its tokens are valid, its score is -inf.  Steps 2-4 run
+ * on the device inside the captured step (two launches in the place of the draw); nothing is read back and no noise is read or
+ * generated.  The selection is a function of the candidate table alone: a session repeats bit for bit.
+ *
+ * A beam session always records, whatever HD_RECORD_LOGP says: hd_sample_logp returns the raw logp[b, t] above, the step value of the
+ * candidate row b became at position t; it is NOT permuted by later steps (follow `parent` backwards to read a final row's history).
+ * hd_beam_state copies score [B], parent [B, Tmax] and cand [B, 22] out (each pointer may be NULL), rows in whole-batch order whatever
+ * the lane split; cand is the candidate table of the last position run (unspecified before the first).  Legal where hd_sample_logp is;
+ * outside a beam session -> HD_ERR_STATE.
+ *
+ * Lifetime: as the block size -- one-shot: the NEXT hd_sample_begin / hd_sample consumes the width whether it succeeds or fails;
+ * hd_sample_restart and the guards' repeats keep it (and start from the initial state again); hd_forward neither uses nor clears it.
+ * Width 0 clears a width not yet consumed.  Inside an open session -> HD_ERR_STATE; a NULL handle or a width outside [0, 64] ->
+ * HD_ERR_INVALID.
+ *
+ * At the begin: B % W != 0 -> HD_ERR_INVALID; a row that differs from the first row of its group in tokens, region, chain,
+ * order[b, 0:T[b]] or T -> HD_ERR_INVALID; q_noise != NULL -> HD_ERR_INVALID; a guide with temperature 0 -> HD_ERR_INVALID (as for
+ * scoring).  A guide and a truncation compose with the beam, both per order position as in a sampling session.  A block size > 1 or
+ * HD_SLOTS_CONFIDENT -> HD_ERR_UNSUPPORTED; hd_score_begin / hd_score with a width pending consume it and return HD_ERR_UNSUPPORTED.
+ * Dropout must be off (HD_DROPOUT_OFF, or cfg.dropout == 0), anything else -> HD_ERR_UNSUPPORTED: generated masks are keyed by row, so
+ * the rows of a group would be ranked under different sub-networks.  Lanes are cut at group boundaries, balanced over groups, at
+ * most G of them.  hd_sample_run(t0, t1) takes any 0 <= t0 < t1 <= Tmax, as at K = 1. */
+HdStatus hd_set_beam(HdModel* m, int32_t width);   /* 0 clears */
+HdStatus hd_beam_state(HdModel* m, float* score /* [B] */, int32_t* parent /* [B, Tmax] */, float* cand /* [B, 22] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
