@@ -18,6 +18,8 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 
 using namespace hd;
@@ -164,6 +166,37 @@ static bool opt_legal(const OptDef& d, int64_t v) {
     return false;
 }
 
+// What a begin can be armed with (the hd_set_* functions write HdModel::pending) and what an open session runs under (HdModel::s).
+// A new option is one field here -- and one term of tied(), which is what the key of the captured step compares.
+struct SessionOpts {
+    int mode = DRAW_SAMPLE;                          // draw stage: plain, recording (HD_RECORD_LOGP, beam), teacher-forced (hd_score_begin); set by the begin
+    int guide = GUIDE_NONE;                          // guided sampling: unguided, allowed bits only, bits and bias
+    float temp = 1.f;                                // its temperature (a kernel argument)
+    int K = 1;                                       // block decoding: slots per step (1: pruned tail + one-slot draw; > 1: full last block + block draw)
+    int policy = HD_SLOTS_GIVEN;                     // slot policy (HD_SLOTS_CONFIDENT: slot_conf_k + slot_select_k in front of the block draw)
+    bool trunc = false;                              // truncated sampling; a truncated session always draws with the guided kernels (guide != GUIDE_NONE)
+    TruncP tr{0, 1.f, 0.f};                          // its normalised parameters (kernel arguments)
+    int W = 0;                                       // beam width; 0 = a draw, > 0: beam_cand_k + beam_select_k in its place
+    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W); }
+    bool operator==(const SessionOpts& o) const { return tied() == o.tied(); }
+};
+
+// Everything the captured step of a lane depends on: a step graph is replayed only while the key it was captured under equals the
+// session's (step_key).  A launch argument or a kernel choice that is missing here replays a stale graph.
+struct StepKey {
+    bool captured = false;                           // false: no graph (Lane::drop_graphs), equal to no session's key
+    int B = 0;                                       // rows of the lane
+    uint32_t no_prune = 0;                           // HD_NO_PRUNE of the session's flags
+    int drop = 0, Tmax = 0;                          // dropout mode, steps of the order lists
+    bool has_q = false; const float* qptr = nullptr; // injected noise and the buffer the draw reads it from
+    int qB = 0, qoff = 0;                            // rows of the whole batch, row offset of the lane
+    int kernels = 0;                                 // kernel_set(): split kernels in use, ln_sync level, lane count
+    SessionOpts o;                                   // (normalised: temperature 1 when unguided, the neutral TruncP when not truncated)
+    const uint32_t* gallow = nullptr; const float* gbias = nullptr;     // the guide buffers the launch really reads: when guided / biased
+    auto tied() const { return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias); }
+    bool operator==(const StepKey& k) const { return tied() == k.tied(); }
+};
+
 struct HdModel {
     HdConfig cfg{};
     int device = 0;
@@ -218,17 +251,7 @@ struct HdModel {
         int B = 0, row_off = 0;                      // rows of the open session handled by this lane
         hipGraph_t graph = nullptr;
         hipGraphExec_t graph_exec = nullptr;
-        int graph_B = -1; uint32_t graph_flags = 0; int graph_drop = -1; bool graph_q = false; int graph_Tmax = -1;
-        int graph_qB = -1, graph_qoff = -1;
-        int graph_x3 = -1;                           // kernel_set() when the graph was captured (split kernels in use, ln_sync level)
-        int graph_mode = -1;                         // draw mode of the captured step (DRAW_SAMPLE / DRAW_RECORD / DRAW_SCORE)
-        int graph_policy = -1;                       // slot policy of the captured step (HD_SLOTS_CONFIDENT: slot_conf_k + slot_select_k in front of the block draw)
-        int graph_W = -1;                            // beam width of the captured step (0: a draw; > 0: beam_cand_k + beam_select_k in its place)
-        int graph_K = -1;                            // slots per step of the captured step (1: pruned tail + sample_step_k; > 1: full last block + sample_block_k)
-        const float* graph_qptr = nullptr;           // the injected-noise buffer the captured sample_step_k reads
-        // the guide the captured draw was launched with (GUIDE_*, its temperature -- a kernel argument -- and the buffers it reads)
-        bool graph_trunc = false; TruncP graph_tr{0, 1.f, 0.f};   // truncation of the captured step (its three parameters are kernel arguments)
-        int graph_guide = -1; float graph_temp = 1.f; const uint32_t* graph_gallow = nullptr; const float* graph_gbias = nullptr;
+        StepKey graph_key;                           // what `graph` was captured under (hd_sample_run)
         // the T-step loop as ONE graph: `loop_steps` child-graph nodes of `graph` in a chain (hd_sample_run)
         hipGraph_t loop_graph = nullptr;
         hipGraphExec_t loop_exec = nullptr;
@@ -239,7 +262,7 @@ struct HdModel {
             loop_steps = 0;
             if (graph_exec) { hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
             if (graph) { hipGraphDestroy(graph); graph = nullptr; }
-            graph_B = -1;
+            graph_key = StepKey();
         }
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
     } lane[HD_MAX_LANES];
@@ -253,31 +276,14 @@ struct HdModel {
     int s_steps = 0;                                 // steps enqueued since then (largest t1 of hd_sample_run)
     uint32_t sflags = 0;
     bool s_has_q = false;
-    int s_mode = DRAW_SAMPLE;                        // draw stage of the session: plain, recording (HD_RECORD_LOGP), teacher-forced (hd_score_begin)
     bool logp_ready = false;                         // the lanes' logp buffers hold a finished recording session (hd_sample_logp after the end)
-    // guided sampling (include/hudiff_hip.h "guided sampling"): hd_set_guide leaves a copy here; the next begin takes it (whether it
-    // succeeds or fails) and, if it succeeds, the session keeps it on the device through restarts and guard repeats
-    struct Guide { int32_t B = 0; float temperature = 1.f; bool has_allow = false, has_bias = false; std::vector<uint32_t> allow; std::vector<float> bias; };
-    bool guide_pending = false;
+    // Session options (include/hudiff_hip.h "guided sampling", "block decoding", "slot policy", "truncated sampling", "beam search"): the
+    // hd_set_* functions leave them in `pending`, hd_set_guide its validated copy of the guide beside it; the next begin takes both
+    // (whether it succeeds or fails) and, if it succeeds, the session keeps them in `s` -- the guide on the device -- through restarts
+    // and guard repeats.  After the end `s` describes the last session (hd_sample_logp, hd_beam_state).
+    struct Guide { int32_t B = 0; bool has_allow = false; std::vector<uint32_t> allow; std::vector<float> bias; };
+    SessionOpts pending, s;
     Guide guide;
-    int s_guide = GUIDE_NONE;                        // draw of the open session: unguided, allowed bits only, bits and bias
-    float s_temp = 1.f;
-    // block decoding (include/hudiff_hip.h "block decoding"): hd_set_slots_per_step leaves K here; the next begin takes it (whether it
-    // succeeds or fails) and, if it succeeds, the session keeps it through restarts and guard repeats
-    int k_next = 1;
-    int sK = 1;                                      // slots per step of the open session
-    // slot policy (include/hudiff_hip.h "slot policy"): hd_set_slot_policy leaves it here; the next begin takes it like the block size
-    int policy_next = HD_SLOTS_GIVEN;
-    int s_policy = HD_SLOTS_GIVEN;                   // slot policy of the open session
-    // truncated sampling (include/hudiff_hip.h "truncated sampling"): hd_set_truncation leaves the normalised parameters here; the next
-    // begin takes them like the block size.  A truncated session always draws with the guided kernels (s_guide != GUIDE_NONE).
-    bool trunc_pending = false;
-    TruncP trunc_next{0, 1.f, 0.f};
-    bool s_trunc = false;                            // the open session truncates
-    TruncP s_tr{0, 1.f, 0.f};
-    // beam search (include/hudiff_hip.h "beam search"): hd_set_beam leaves the width here; the next begin takes it like the block size
-    int beam_next = 0;
-    int sW = 0;                                      // beam width of the open (or last) session; 0 = not a beam session
     std::vector<float> beam_score0;                  // score of every row at the begin: 0 for the first row of a group, -inf for the others
     bool order_ready = false;                        // the lanes' order buffers hold an ended session's order (hd_sample_order after the end)
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
@@ -643,7 +649,7 @@ extern "C" HdStatus hd_set_slots_per_step(HdModel* m, int32_t k) {
     if (!m) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: null model");
     if (k < 1 || k > 64) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: k = %d outside [1, 64]", k);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slots_per_step: a sampling session is open (the block size belongs to the NEXT begin)");
-    m->k_next = k;
+    m->pending.K = k;
     return HD_OK;
 }
 
@@ -652,7 +658,7 @@ extern "C" HdStatus hd_set_beam(HdModel* m, int32_t width) {
     if (!m) return fail(HD_ERR_INVALID, "hd_set_beam: null model");
     if (width < 0 || width > BEAM_MAX_W) return fail(HD_ERR_INVALID, "hd_set_beam: width = %d outside [0, %d]", width, BEAM_MAX_W);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_beam: a sampling session is open (the width belongs to the NEXT begin)");
-    m->beam_next = width;
+    m->pending.W = width;
     return HD_OK;
 }
 
@@ -661,7 +667,7 @@ extern "C" HdStatus hd_set_slot_policy(HdModel* m, int32_t policy) {
     if (!m) return fail(HD_ERR_INVALID, "hd_set_slot_policy: null model");
     if (policy != HD_SLOTS_GIVEN && policy != HD_SLOTS_CONFIDENT) return fail(HD_ERR_INVALID, "hd_set_slot_policy: unknown policy %d", policy);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slot_policy: a sampling session is open (the policy belongs to the NEXT begin)");
-    m->policy_next = policy;
+    m->pending.policy = policy;
     return HD_OK;
 }
 
@@ -669,8 +675,8 @@ extern "C" HdStatus hd_set_slot_policy(HdModel* m, int32_t policy) {
 extern "C" HdStatus hd_set_truncation(HdModel* m, const HdTruncation* t) {
     if (!m) return fail(HD_ERR_INVALID, "hd_set_truncation: null model");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_truncation: a sampling session is open (the truncation belongs to the NEXT begin)");
-    m->trunc_pending = false;
-    m->trunc_next = TruncP{0, 1.f, 0.f};
+    m->pending.trunc = false;
+    m->pending.tr = TruncP{0, 1.f, 0.f};
     if (!t) return HD_OK;
     if (t->top_k < 0 || t->top_k > 22) return fail(HD_ERR_INVALID, "hd_set_truncation: top_k = %d outside [0, 22]", t->top_k);
     if (!(t->top_p > 0.f && t->top_p <= 1.f))        // (NaN fails every comparison)
@@ -678,8 +684,8 @@ extern "C" HdStatus hd_set_truncation(HdModel* m, const HdTruncation* t) {
     if (!(t->min_p >= 0.f && t->min_p <= 1.f)) return fail(HD_ERR_INVALID, "hd_set_truncation: min_p = %g outside [0, 1]", (double)t->min_p);
     const TruncP tr{t->top_k >= 22 ? 0 : t->top_k, t->top_p, t->min_p};
     if (tr.top_k == 0 && tr.top_p >= 1.f && tr.min_p == 0.f) return HD_OK;      // nothing is cut: the session launches the kernels it always did
-    m->trunc_next = tr;
-    m->trunc_pending = true;
+    m->pending.tr = tr;
+    m->pending.trunc = true;
     return HD_OK;
 }
 
@@ -688,7 +694,8 @@ extern "C" HdStatus hd_set_guide(HdModel* m, const HdGuide* g) {
     if (!m) return fail(HD_ERR_INVALID, "hd_set_guide: null model");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_guide: a sampling session is open (the guide belongs to the NEXT begin)");
     m->guide = HdModel::Guide();
-    m->guide_pending = false;
+    m->pending.guide = GUIDE_NONE;
+    m->pending.temp = 1.f;
     if (!g) return HD_OK;
     if (g->B < 0) return fail(HD_ERR_INVALID, "hd_set_guide: B = %d", g->B);
     const float tp = g->temperature;
@@ -701,10 +708,11 @@ extern "C" HdStatus hd_set_guide(HdModel* m, const HdGuide* g) {
                 return fail(HD_ERR_INVALID, "hd_set_guide: bias[%zu, %zu, %zu] is not finite (forbid a token through `allow`)",
                             i / 22 / m->L, i / 22 % m->L, i % 22);
     HdModel::Guide& k = m->guide;
-    k.B = g->B; k.temperature = tp; k.has_allow = g->allow != nullptr; k.has_bias = g->bias != nullptr;
+    k.B = g->B; k.has_allow = g->allow != nullptr;
     if (g->allow) k.allow.assign(g->allow, g->allow + n);
     if (g->bias) k.bias.assign(g->bias, g->bias + n * 22);
-    m->guide_pending = true;
+    m->pending.guide = g->bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW;
+    m->pending.temp = tp;
     return HD_OK;
 }
 
@@ -1846,49 +1854,60 @@ extern "C" HdStatus hd_forward(HdModel* m, const int32_t* tokens, const int32_t*
 }
 
 // ---- sampling session ---------------------------------------------------------------------------
-// Draw stage of a block session: K order positions per forward, one workgroup per (row, position) on the full hidden buffer.
-static HdStatus block_draw(HdModel* m, const Segs& sg) {
+// The draw stage, and what stands in front of it (slot_choose) or in its place (beam_step).  A run-time choice of the session becomes
+// a template argument in one place: static_switch over the draw mode and over the guide level of the launch.
+enum { LV_PLAIN = 0, LV_GUIDED = 1, LV_TRUNC = 2 };  // no guide, guided, guided + truncation (a truncated session is always guided: sample_begin_impl)
+static int guide_level(const HdModel* m) { return m->s.trunc ? LV_TRUNC : m->s.guide != GUIDE_NONE ? LV_GUIDED : LV_PLAIN; }
+
+// f(std::integral_constant<int, v>{}) for a v in [0, N)
+template <int N, int I = 0, typename F>
+static void static_switch(int v, F&& f) {
+    if constexpr (I < N) {
+        if (v == I) f(std::integral_constant<int, I>{});
+        else static_switch<N, I + 1>(v, f);
+    }
+}
+
+// The guide argument of a launch at level LV: GuideP (the neutral one without a guide), GuideTP when the launch truncates.
+template <int LV>
+static auto guide_arg(const HdModel* m) {
+    if constexpr (LV == LV_PLAIN) {
+        return GuideP{nullptr, nullptr, 1.f};
+    } else {
+        const Workspace& ws = cur(m).ws;
+        const GuideP g{ws.gallow, m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s.temp};
+        if constexpr (LV == LV_TRUNC) return GuideTP{g, m->s.tr};
+        else return g;
+    }
+}
+
+// The draw, sample_step_k: one workgroup per (row, order position of this forward), grid (B, K), whose last one advances the step by K.
+// prune: the compact rows of a pruned tail (K == 1 only: one_step); otherwise the full hidden buffer.  The injected Exp(1) noise lives
+// once, for the whole batch, in the model (m->qnoise).
+static HdStatus draw(HdModel* m, const Segs& sg, bool prune) {
     HdModel::Lane& ln = cur(m);
     Workspace& ws = ln.ws;
+    const float* hm = prune ? ws.Xc : ws.Y;
     const float* qn = m->s_has_q ? m->qnoise : nullptr;
-    const dim3 grid(sg.B, m->sK), block(64 * SS_WAVES);
-    if (m->s_trunc) {                                // (a truncated session is always guided: sample_begin_impl)
-        const GuideTP g{GuideP{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp}, m->s_tr};
-        if (m->s_mode == DRAW_SAMPLE)
-            hipLaunchKernelGGL((sample_block_guided_k<DRAW_SAMPLE, true>), grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, (float*)nullptr, (const int32_t*)nullptr, g);
-        else if (m->s_mode == DRAW_RECORD)
-            hipLaunchKernelGGL((sample_block_guided_k<DRAW_RECORD, true>), grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
-        else
-            hipLaunchKernelGGL((sample_block_guided_k<DRAW_SCORE, true>), grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
-    } else if (m->s_guide != GUIDE_NONE) {
-        const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
-        if (m->s_mode == DRAW_SAMPLE)
-            hipLaunchKernelGGL(sample_block_guided_k<DRAW_SAMPLE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, (float*)nullptr, (const int32_t*)nullptr, g);
-        else if (m->s_mode == DRAW_RECORD)
-            hipLaunchKernelGGL(sample_block_guided_k<DRAW_RECORD>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
-        else
-            hipLaunchKernelGGL(sample_block_guided_k<DRAW_SCORE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target, g);
-    } else if (m->s_mode == DRAW_SAMPLE)
-        hipLaunchKernelGGL(sample_block_k, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                           qn, m->sB, ln.row_off, ln.rs, sg);
-    else if (m->s_mode == DRAW_RECORD)
-        hipLaunchKernelGGL(sample_block_logp_k<DRAW_RECORD>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                           qn, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target);
-    else
-        hipLaunchKernelGGL(sample_block_logp_k<DRAW_SCORE>, grid, block, 0, ln.stream, ws.Y, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                           (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, ws.logp, (const int32_t*)ws.target);
+    const bool rec = m->s.mode != DRAW_SAMPLE;
+    float* logp = rec ? ws.logp : nullptr;
+    const int32_t* target = rec ? ws.target : nullptr;
+    const int compact = prune ? 1 : 0;
+    const dim3 grid(sg.B, m->s.K), threads(64 * SS_WAVES);
+    static_switch<3>(guide_level(m), [&](auto lv) {
+        static_switch<3>(m->s.mode, [&](auto mode) {
+            constexpr int LV = decltype(lv)::value, MODE = decltype(mode)::value;
+            const auto guide = [&] { if constexpr (LV == LV_PLAIN) return NoGuide{}; else return guide_arg<LV>(m); }();
+            hipLaunchKernelGGL((sample_step_k<MODE, LV != LV_PLAIN, LV == LV_TRUNC>), grid, threads, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
+                               ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, compact, logp, target, guide);
+        });
+    });
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
 
 // Selection stage of a confident session (HD_SLOTS_CONFIDENT): keys of every remaining position from this forward's hidden rows, then the
-// K best of each row move to the front of its order -- with what is keyed by their positions -- for block_draw to fill.
+// K best of each row move to the front of its order -- with what is keyed by their positions -- for the draw to fill.
 static HdStatus slot_choose(HdModel* m, const Segs& sg) {
     HdModel::Lane& ln = cur(m);
     Workspace& ws = ln.ws;
@@ -1897,26 +1916,16 @@ static HdStatus slot_choose(HdModel* m, const Segs& sg) {
     if (npos <= 0) return HD_OK;
     const dim3 cgrid((npos + SC_WAVES - 1) / SC_WAVES, sg.B), cblock(64 * SC_WAVES);
     const size_t lds = (size_t)SC_HALF * m->D * sizeof(float);
-    int32_t* tg = m->s_mode == DRAW_SCORE ? ws.target : nullptr;
-    if (m->s_trunc) {
-        const GuideTP g{GuideP{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp}, m->s_tr};
-        hipLaunchKernelGGL((slot_conf_k<true, true>), cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf, g);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(slot_select_k<true>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, tg, ws.T, m->sTmax, m->sK, ln.rs, ws.conf,
-                           ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : (float*)nullptr);
-    } else if (m->s_guide != GUIDE_NONE) {
-        const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
-        hipLaunchKernelGGL(slot_conf_k<true>, cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf, g);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(slot_select_k<true>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, tg, ws.T, m->sTmax, m->sK, ln.rs, ws.conf,
-                           ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : (float*)nullptr);
-    } else {
-        hipLaunchKernelGGL(slot_conf_k<false>, cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, ws.conf,
-                           GuideP{nullptr, nullptr, 1.f});
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(slot_select_k<false>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, tg, ws.T, m->sTmax, m->sK, ln.rs, ws.conf,
-                           (uint32_t*)nullptr, (float*)nullptr);
-    }
+    static_switch<3>(guide_level(m), [&](auto lv) {
+        constexpr int LV = decltype(lv)::value;
+        hipLaunchKernelGGL((slot_conf_k<LV != LV_PLAIN, LV == LV_TRUNC>), cgrid, cblock, lds, ln.stream, ws.Y, m->D, m->head, ws.order, ws.T, m->sTmax,
+                           ln.rs, sg, ws.conf, guide_arg<LV>(m));
+    });
+    HIP_TRY(hipGetLastError());
+    const bool guided = m->s.guide != GUIDE_NONE;
+    hipLaunchKernelGGL(guided ? slot_select_k<true> : slot_select_k<false>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order,
+                       m->s.mode == DRAW_SCORE ? ws.target : nullptr, ws.T, m->sTmax, m->s.K, ln.rs, ws.conf, guided ? ws.gallow : nullptr,
+                       m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -1927,132 +1936,76 @@ static HdStatus beam_step(HdModel* m, const Segs& sg, bool prune) {
     HdModel::Lane& ln = cur(m);
     Workspace& ws = ln.ws;
     static_assert(BEAM_MAX_L >= 304, "beam_select_k stages whole token rows (max_len <= 304, hd_create)");
-    const float* hm = prune ? ws.Xc : ws.Y;
-    const dim3 grid(sg.B), block(64 * SS_WAVES);
-    const int compact = prune ? 1 : 0;
-    const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
-    if (m->s_trunc)
-        hipLaunchKernelGGL((beam_cand_k<true, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, compact,
-                           ws.bscore, ws.bcand, ws.blp, GuideTP{g, m->s_tr});
-    else if (m->s_guide != GUIDE_NONE)
-        hipLaunchKernelGGL(beam_cand_k<true>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, compact,
-                           ws.bscore, ws.bcand, ws.blp, g);
-    else
-        hipLaunchKernelGGL(beam_cand_k<false>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.order, ws.T, m->sTmax, ln.rs, sg, compact,
-                           ws.bscore, ws.bcand, ws.blp, GuideP{nullptr, nullptr, 1.f});
+    static_switch<3>(guide_level(m), [&](auto lv) {
+        constexpr int LV = decltype(lv)::value;
+        hipLaunchKernelGGL((beam_cand_k<LV != LV_PLAIN, LV == LV_TRUNC>), dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, prune ? ws.Xc : ws.Y, m->D, m->head,
+                           ws.order, ws.T, m->sTmax, ln.rs, sg, prune ? 1 : 0, ws.bscore, ws.bcand, ws.blp, guide_arg<LV>(m));
+    });
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(beam_select_k, dim3(sg.B / m->sW), dim3(BEAM_THREADS), 0, ln.stream, ws.tokens, ws.order, ws.T, m->sTmax, m->L, m->sW, ln.rs,
+    hipLaunchKernelGGL(beam_select_k, dim3(sg.B / m->s.W), dim3(BEAM_THREADS), 0, ln.stream, ws.tokens, ws.order, ws.T, m->sTmax, m->L, m->s.W, ln.rs,
                        ws.bscore, ws.bparent, ws.logp, ws.bcand, ws.blp);
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
 
 static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, const uint8_t* cm) {
-    HdModel::Lane& ln = cur(m);
     // a block session (K > 1) visits K rows per sequence: the last attention block runs for every row, as with HD_NO_PRUNE; so does a
     // confident session at any K, whose selection needs the hidden row of every remaining slot
-    const bool confident = m->s_policy == HD_SLOTS_CONFIDENT;
-    const bool prune = !(m->sflags & HD_NO_PRUNE) && m->sK == 1 && !confident;
+    const bool confident = m->s.policy == HD_SLOTS_CONFIDENT;
+    const bool prune = !(m->sflags & HD_NO_PRUNE) && m->s.K == 1 && !confident;
     HD_TRY(forward_body(m, sg, dm, em, cm, prune));
-    Workspace& ws = ln.ws;
-    if (m->sW > 0) return beam_step(m, sg, prune);   // (a beam session has K = 1 and the given order: sample_begin_impl)
+    if (m->s.W > 0) return beam_step(m, sg, prune);  // (a beam session has K = 1 and the given order: sample_begin_impl)
     if (confident) HD_TRY(slot_choose(m, sg));
-    if (m->sK > 1 || confident) return block_draw(m, sg);       // (K = 1: gridDim.y == 1, position `step`)
-    // the injected Exp(1) noise lives once, for the whole batch, in the model (m->qnoise)
-    // (the last workgroup of sample_step_k advances the step)
-    const float* hm = prune ? ws.Xc : ws.Y;
-    const float* qn = m->s_has_q ? m->qnoise : nullptr;
-    if (m->s_trunc) {
-        const GuideTP g{GuideP{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp}, m->s_tr};
-        const dim3 grid(sg.B), block(64 * SS_WAVES);
-        const int compact = prune ? 1 : 0;
-        if (m->s_mode == DRAW_SAMPLE)
-            hipLaunchKernelGGL((sample_step_guided_k<DRAW_SAMPLE, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, (float*)nullptr, (const int32_t*)nullptr, g);
-        else if (m->s_mode == DRAW_RECORD)
-            hipLaunchKernelGGL((sample_step_guided_k<DRAW_RECORD, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
-        else
-            hipLaunchKernelGGL((sample_step_guided_k<DRAW_SCORE, true>), grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
-    } else if (m->s_guide != GUIDE_NONE) {
-        const GuideP g{ws.gallow, m->s_guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s_temp};
-        const dim3 grid(sg.B), block(64 * SS_WAVES);
-        const int compact = prune ? 1 : 0;
-        if (m->s_mode == DRAW_SAMPLE)
-            hipLaunchKernelGGL(sample_step_guided_k<DRAW_SAMPLE>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, (float*)nullptr, (const int32_t*)nullptr, g);
-        else if (m->s_mode == DRAW_RECORD)
-            hipLaunchKernelGGL(sample_step_guided_k<DRAW_RECORD>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               qn, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
-        else
-            hipLaunchKernelGGL(sample_step_guided_k<DRAW_SCORE>, grid, block, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order, ws.T, m->sTmax,
-                               (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, compact, 1, ws.logp, (const int32_t*)ws.target, g);
-    } else if (m->s_mode == DRAW_SAMPLE)
-        hipLaunchKernelGGL(sample_step_k, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
-                           ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1);
-    else if (m->s_mode == DRAW_RECORD)
-        hipLaunchKernelGGL(sample_step_logp_k<DRAW_RECORD>, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
-                           ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1, ws.logp, (const int32_t*)ws.target);
-    else
-        hipLaunchKernelGGL(sample_step_logp_k<DRAW_SCORE>, dim3(sg.B), dim3(64 * SS_WAVES), 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
-                           ws.T, m->sTmax, (const float*)nullptr, m->sB, ln.row_off, ln.rs, sg, prune ? 1 : 0, 1, ws.logp, (const int32_t*)ws.target);
-    HIP_TRY(hipGetLastError());
-    return HD_OK;
+    return draw(m, sg, prune);
 }
 
-static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
-                                  const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
-                                  uint64_t seed, uint64_t row0, const float* q_noise,
-                                  const uint8_t* enc_masks, const uint8_t* conv_masks, bool score, const HdModel::Guide* guide, int K,
-                                  int policy, const TruncP* trunc, int W) {
-    if (!m || !tokens || !region || !T || (Tmax > 0 && !order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
-    if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
-    if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
-    if (B < 0 || Tmax < 0) return fail(HD_ERR_INVALID, "hd_sample_begin: B = %d, Tmax = %d", B, Tmax);
-    HIP_TRY(hipSetDevice(m->device));
-    m->sB = B; m->sTmax = Tmax; m->sflags = flags; m->s_has_q = q_noise != nullptr; m->timed = false; m->last_steps = 0;
-    m->s_seed = seed; m->s_steps = 0; m->s_dirty = false;
-    m->nlanes = 1; m->cl = 0;
-    m->s_mode = score ? DRAW_SCORE : ((flags & HD_RECORD_LOGP) || W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
-    m->sW = 0;
-    m->logp_ready = false;
-    m->order_ready = false;
-    m->s_guide = GUIDE_NONE; m->s_temp = 1.f;
-    m->sK = 1;
-    m->s_policy = HD_SLOTS_GIVEN;
-    m->s_trunc = false; m->s_tr = TruncP{0, 1.f, 0.f};
-    // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
-    // bias, temperature 1), under which g_j == logit_j bit for bit
-    HdModel::Guide neutral;
-    if (trunc && !guide) { neutral.B = B; guide = &neutral; }
-    const bool confident = policy == HD_SLOTS_CONFIDENT;
+// ---- the begin of a session, in parts ------------------------------------------------------------
+// What the caller of hd_sample_begin / hd_score_begin passed.
+struct BeginIn {
+    const int32_t *tokens, *region, *chain, *order, *T;
+    int32_t B, Tmax;
+    uint32_t flags;
+    uint64_t seed, row0;
+    const float* q_noise;
+    const uint8_t *enc_masks, *conv_masks;
+    bool score;                                      // hd_score_begin
+};
+
+// The options against each other and against the call.
+static HdStatus check_options(const HdModel* m, const BeginIn& in, const SessionOpts& o, const HdModel::Guide& guide) {
+    const int B = in.B, K = o.K, W = o.W;
+    const bool confident = o.policy == HD_SLOTS_CONFIDENT, guided = o.guide != GUIDE_NONE;
     if (W > 0) {                                     // beam search: one slot per forward in the given order, no noise, no dropout
-        if (score) return fail(HD_ERR_UNSUPPORTED, "hd_score_begin: a beam width is set (hd_set_beam); a scoring session has no beam");
+        if (in.score) return fail(HD_ERR_UNSUPPORTED, "hd_score_begin: a beam width is set (hd_set_beam); a scoring session has no beam");
         if (K > 1 || confident)
             return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a beam session takes one slot per forward in the given order (slots per step %d%s)",
                         K, confident ? ", confident slot policy" : "");
-        if (drop_mode_of(m, flags) != DROP_NONE)
+        if (drop_mode_of(m, in.flags) != DROP_NONE)
             return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a beam session runs with dropout off (HD_DROPOUT_OFF, or cfg.dropout == 0): generated "
                                             "masks are keyed by row, so the rows of a group would be ranked under different sub-networks");
-        if (q_noise) return fail(HD_ERR_INVALID, "hd_sample_begin: a beam session reads no noise (q_noise must be NULL)");
-        if (guide && guide->temperature == 0.f)
+        if (in.q_noise) return fail(HD_ERR_INVALID, "hd_sample_begin: a beam session reads no noise (q_noise must be NULL)");
+        if (guided && o.temp == 0.f)
             return fail(HD_ERR_INVALID, "hd_sample_begin: a guide with temperature 0 (greedy decode) has no distribution for a beam to rank under");
         if (B % W != 0) return fail(HD_ERR_INVALID, "hd_sample_begin: %d rows are not whole groups of beam width %d", B, W);
     }
-    if (confident && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
+    if (confident && (in.flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
         return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop in the given order; a "
                                         "confident session takes generated masks or none");
-    if (K > 1 && (flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
+    if (K > 1 && (in.flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
         return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop; a session with "
                                         "%d slots per step takes generated masks or none", K);
-    if (guide) {
-        if (guide->B != B) return fail(HD_ERR_INVALID, "hd_set_guide: the guide describes %d rows, the session has %d", guide->B, B);
-        if (score && guide->temperature == 0.f)
+    if (guided) {
+        if (guide.B != B) return fail(HD_ERR_INVALID, "hd_set_guide: the guide describes %d rows, the session has %d", guide.B, B);
+        if (in.score && o.temp == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
     }
-    if (B == 0) { m->sK = K; m->s_policy = policy; m->sW = W; m->in_session = true; return HD_OK; }      // (no row: nothing to guide or truncate)
-    HD_TRY(validate_inputs(m, tokens, region, chain, B));
+    return HD_OK;
+}
+
+// The order lists: ranges, repeats inside a group of K, the groups of a beam, the candidate set of a confident session.
+static HdStatus check_orders(const HdModel* m, const BeginIn& in, const SessionOpts& o) {
+    const int B = in.B, Tmax = in.Tmax, K = o.K, W = o.W;
+    const int32_t *order = in.order, *T = in.T;
     for (int b = 0; b < B; ++b) {
         if (T[b] < 0 || T[b] > Tmax) return fail(HD_ERR_INVALID, "T[%d] = %d out of [0,%d]", b, T[b], Tmax);
         for (int t = 0; t < T[b]; ++t) {
@@ -2071,14 +2024,14 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
     for (int b = 0; W > 0 && b < B; ++b) {
         const int a = b / W * W;
         if (a == b) continue;
-        bool same = T[b] == T[a] && memcmp(tokens + (size_t)b * m->L, tokens + (size_t)a * m->L, (size_t)m->L * sizeof(int32_t)) == 0 &&
-                    memcmp(region + (size_t)b * m->L, region + (size_t)a * m->L, (size_t)m->L * sizeof(int32_t)) == 0;
+        bool same = T[b] == T[a] && memcmp(in.tokens + (size_t)b * m->L, in.tokens + (size_t)a * m->L, (size_t)m->L * sizeof(int32_t)) == 0 &&
+                    memcmp(in.region + (size_t)b * m->L, in.region + (size_t)a * m->L, (size_t)m->L * sizeof(int32_t)) == 0;
         if (same && T[b] > 0) same = memcmp(order + (size_t)b * Tmax, order + (size_t)a * Tmax, (size_t)T[b] * sizeof(int32_t)) == 0;
-        if (same && m->nseg > 1) same = chain[b] == chain[a] && chain[B + b] == chain[B + a];
+        if (same && m->nseg > 1) same = in.chain[b] == in.chain[a] && in.chain[B + b] == in.chain[B + a];
         if (!same) return fail(HD_ERR_INVALID, "hd_sample_begin: row %d differs from row %d, the first of its beam group (tokens, region, chain, order and T must be equal)", b, a);
     }
     // slot policy: the candidate list of a confident session is a set -- any of its slots may meet any other in one group
-    if (confident) {
+    if (o.policy == HD_SLOTS_CONFIDENT) {
         std::vector<int> seen((size_t)m->L);
         for (int b = 0; b < B; ++b) {
             std::fill(seen.begin(), seen.end(), -1);
@@ -2091,252 +2044,247 @@ static HdStatus sample_begin_impl(HdModel* m, const int32_t* tokens, const int32
             }
         }
     }
-    // scoring: the caller's tokens are complete; the slots to score become the targets and are masked in the library's copy
-    std::vector<int32_t> masked, target;
-    if (score) {
-        masked.assign(tokens, tokens + (size_t)B * m->L);
-        target.assign((size_t)B * (Tmax > 0 ? Tmax : 1), 0);
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < T[b]; ++t) {
-                const int s = order[(size_t)b * Tmax + t], x = tokens[(size_t)b * m->L + s];
-                if (x < 0 || x > 21) return fail(HD_ERR_INVALID, "hd_score_begin: token %d at row %d slot %d (step %d) is not a residue or gap in [0,21]", x, b, s, t);
-                target[(size_t)b * Tmax + t] = x;
-            }
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < T[b]; ++t) masked[(size_t)b * m->L + order[(size_t)b * Tmax + t]] = 22;
-        tokens = masked.data();
-    }
-    // the guide, gathered by step (only visited slots are looked at): gallow [B, Tmax], gbias [B, Tmax, 22]
-    std::vector<uint32_t> gallow;
-    std::vector<float> gbias;
-    if (guide) {
-        const size_t Tm = Tmax > 0 ? Tmax : 1;
-        gallow.assign((size_t)B * Tm, 0u);
-        if (guide->has_bias) gbias.assign((size_t)B * Tm * 22, 0.f);
-        for (int b = 0; b < B; ++b)
-            for (int t = 0; t < T[b]; ++t) {
-                const int s = order[(size_t)b * Tmax + t];
-                const uint32_t a = (guide->has_allow ? guide->allow[(size_t)b * m->L + s] : GUIDE_ALL_TOKENS) & GUIDE_ALL_TOKENS;
-                if (a == 0) return fail(HD_ERR_INVALID, "hd_set_guide: no token is allowed at row %d slot %d (step %d)", b, s, t);
-                if (score && !((a >> target[(size_t)b * Tmax + t]) & 1u))
-                    return fail(HD_ERR_INVALID, "hd_score_begin: token %d at row %d slot %d (step %d) is not allowed by the guide",
-                                target[(size_t)b * Tmax + t], b, s, t);
-                gallow[(size_t)b * Tmax + t] = a;
-                if (guide->has_bias)
-                    memcpy(&gbias[((size_t)b * Tmax + t) * 22], &guide->bias[((size_t)b * m->L + s) * 22], 22 * sizeof(float));
-            }
-    }
-    const int dm = drop_mode_of(m, flags);
-    if (dm == DROP_INJECT && (!enc_masks || !conv_masks)) return fail(HD_ERR_INVALID, "hd_sample_begin: HD_DROPOUT_INJECT needs masks");
-    // two concurrent half-batches unless the batch is small, masks are injected (their layout is per full batch)
-    // or the caller asked for one lane
+    return HD_OK;
+}
+
+// Scoring: the caller's tokens are complete; the slots to score become the targets [B, Tmax] and are masked in the library's copy.
+static HdStatus score_targets(const HdModel* m, const BeginIn& in, std::vector<int32_t>& masked, std::vector<int32_t>& target) {
+    const int B = in.B, Tmax = in.Tmax;
+    masked.assign(in.tokens, in.tokens + (size_t)B * m->L);
+    target.assign((size_t)B * (Tmax > 0 ? Tmax : 1), 0);
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < in.T[b]; ++t) {
+            const int s = in.order[(size_t)b * Tmax + t], x = in.tokens[(size_t)b * m->L + s];
+            if (x < 0 || x > 21) return fail(HD_ERR_INVALID, "hd_score_begin: token %d at row %d slot %d (step %d) is not a residue or gap in [0,21]", x, b, s, t);
+            target[(size_t)b * Tmax + t] = x;
+        }
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < in.T[b]; ++t) masked[(size_t)b * m->L + in.order[(size_t)b * Tmax + t]] = 22;
+    return HD_OK;
+}
+
+// The guide, gathered by step (only visited slots are looked at): gallow [B, Tmax], gbias [B, Tmax, 22].
+static HdStatus gather_guide(const HdModel* m, const BeginIn& in, const SessionOpts& o, const HdModel::Guide& guide,
+                             const std::vector<int32_t>& target, std::vector<uint32_t>& gallow, std::vector<float>& gbias) {
+    const int B = in.B, Tmax = in.Tmax;
+    const bool biased = o.guide == GUIDE_ALLOW_BIAS;
+    const size_t Tm = Tmax > 0 ? Tmax : 1;
+    gallow.assign((size_t)B * Tm, 0u);
+    if (biased) gbias.assign((size_t)B * Tm * 22, 0.f);
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < in.T[b]; ++t) {
+            const int s = in.order[(size_t)b * Tmax + t];
+            const uint32_t a = (guide.has_allow ? guide.allow[(size_t)b * m->L + s] : GUIDE_ALL_TOKENS) & GUIDE_ALL_TOKENS;
+            if (a == 0) return fail(HD_ERR_INVALID, "hd_set_guide: no token is allowed at row %d slot %d (step %d)", b, s, t);
+            if (in.score && !((a >> target[(size_t)b * Tmax + t]) & 1u))
+                return fail(HD_ERR_INVALID, "hd_score_begin: token %d at row %d slot %d (step %d) is not allowed by the guide",
+                            target[(size_t)b * Tmax + t], b, s, t);
+            gallow[(size_t)b * Tmax + t] = a;
+            if (biased) memcpy(&gbias[((size_t)b * Tmax + t) * 22], &guide.bias[((size_t)b * m->L + s) * 22], 22 * sizeof(float));
+        }
+    return HD_OK;
+}
+
+// Two concurrent half-batches (balanced contiguous row blocks) unless the batch is small, masks are injected (their layout is per full
+// batch) or the caller asked for one lane.  A beam session is cut at group boundaries.
+static void split_lanes(HdModel* m, const BeginIn& in, const SessionOpts& o, int dm) {
     const long lane_min_b = m->opt[HD_OPT_LANE_MIN_ROWS];
-    m->nlanes = (B >= lane_min_b && dm != DROP_INJECT && !(flags & HD_ONE_LANE)) ? (int)m->opt[HD_OPT_LANES] : 1;
-    const int unit = W > 0 ? W : 1, nunit = B / unit;  // a beam session is cut at group boundaries
+    m->nlanes = (in.B >= lane_min_b && dm != DROP_INJECT && !(in.flags & HD_ONE_LANE)) ? (int)m->opt[HD_OPT_LANES] : 1;
+    const int unit = o.W > 0 ? o.W : 1, nunit = in.B / unit;
     if (m->nlanes > nunit) m->nlanes = nunit;
-    for (int l = 0, off = 0; l < m->nlanes; ++l) {            // balanced contiguous row blocks
+    for (int l = 0, off = 0; l < m->nlanes; ++l) {
         const int Bl = unit * (nunit / m->nlanes + (l < nunit % m->nlanes ? 1 : 0));
         m->lane[l].B = Bl; m->lane[l].row_off = off;
         off += Bl;
     }
-    if (W > 0) {
-        m->beam_score0.assign((size_t)B, -INFINITY);
-        for (int b = 0; b < B; b += W) m->beam_score0[b] = 0.f;
-    }
-    const auto need_T = [](int Bl, int Tm) { return (size_t)Bl * (Tm > 0 ? Tm : 1); };
+}
+
+// The session buffers of a lane come in three groups that are regrown together; each names its buffers once, as f(pointer, elements).
+// Per (row, step), n = B * Tmax: beside `order` the log-probabilities, targets, allowed bits, confidence keys and the copies a restart reads.
+template <typename F>
+static HdStatus bufs_per_step(Workspace& ws, size_t n, F&& f) {
+    HD_TRY(f(&ws.order, n)); HD_TRY(f(&ws.logp, n)); HD_TRY(f(&ws.target, n)); HD_TRY(f(&ws.gallow, n));
+    HD_TRY(f(&ws.conf, n)); HD_TRY(f(&ws.order0, n)); HD_TRY(f(&ws.target0, n)); HD_TRY(f(&ws.gallow0, n));
+    return HD_OK;
+}
+// The bias of a guide, n = B * Tmax * 22.
+template <typename F>
+static HdStatus bufs_bias(Workspace& ws, size_t n, F&& f) {
+    HD_TRY(f(&ws.gbias, n)); HD_TRY(f(&ws.gbias0, n));
+    return HD_OK;
+}
+// A beam session: score [B], candidate table and step log-probabilities [B, 22], parent [B, Tmax].
+template <typename F>
+static HdStatus bufs_beam(Workspace& ws, size_t nB, size_t nT, F&& f) {
+    HD_TRY(f(&ws.bscore, nB)); HD_TRY(f(&ws.bcand, nB * 22)); HD_TRY(f(&ws.blp, nB * 22)); HD_TRY(f(&ws.bparent, nT));
+    return HD_OK;
+}
+
+// Grows a group: its old buffers are released now, not at the next free_ws, and the lane's graphs go -- a captured step holds the old
+// addresses.  group(f) is one of the three above with its sizes bound.
+template <typename G>
+static HdStatus regrow(HdModel::Lane& ln, G&& group) {
+    Workspace& ws = ln.ws;
+    HIP_TRY(hipStreamSynchronize(ln.stream));
+    group([&](auto** p, size_t) {
+        for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
+            if (*it == (void*)*p) { ws.owned.erase(it); break; }
+        hipFree(*p);
+        *p = nullptr;
+        return HD_OK;
+    });
+    ln.drop_graphs();
+    return group([&](auto** p, size_t n) { return dalloc(ws, p, n); });
+}
+
+// Buffers and uploads of the lane m->cl.
+static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, int dm, const std::vector<int32_t>& target,
+                           const std::vector<uint32_t>& gallow, const std::vector<float>& gbias) {
+    HdModel::Lane& ln = cur(m);
+    const int B = in.B, Tmax = in.Tmax, Bl = ln.B, off = ln.row_off;
+    const bool guided = o.guide != GUIDE_NONE, biased = o.guide == GUIDE_ALLOW_BIAS;
+    HD_TRY(ensure_ws(m, Bl));
+    Workspace& ws = ln.ws;
+    const Segs sg = make_segs(m, Bl);
     std::vector<int32_t> chain_l;
-    for (int l = 0; l < m->nlanes; ++l) {
-        m->cl = l;
-        HdModel::Lane& ln = m->lane[l];
-        const int Bl = ln.B, off = ln.row_off;
-        HD_TRY(ensure_ws(m, Bl));
-        Workspace& ws = ln.ws;
-        const Segs sg = make_segs(m, Bl);
-        const int32_t* ch = nullptr;
-        if (m->nseg > 1) {            // chain[0:B] heavy ids, chain[B:2B] light ids -> this lane's [heavy | light]
-            chain_l.assign((size_t)2 * Bl, 0);
-            for (int b = 0; b < Bl; ++b) { chain_l[b] = chain[off + b]; chain_l[Bl + b] = chain[B + off + b]; }
-            ch = chain_l.data();
-        }
-        HD_TRY(upload_common(m, tokens + (size_t)off * m->L, region + (size_t)off * m->L, ch, Bl));
-        HIP_TRY(hipStreamSynchronize(ln.stream));          // chain_l is reused by the next lane
-        {
-            const size_t need = (size_t)Bl * (Tmax > 0 ? Tmax : 1);
-            if (need > (size_t)ws.capT) {
-                if (ws.order) {                 // regrown: release the old buffers now, not at the next free_ws
-                    HIP_TRY(hipStreamSynchronize(ln.stream));
-                    for (void* old : {(void*)ws.order, (void*)ws.logp, (void*)ws.target, (void*)ws.gallow, (void*)ws.conf, (void*)ws.order0,
-                                      (void*)ws.target0, (void*)ws.gallow0}) {
-                        for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
-                            if (*it == old) { ws.owned.erase(it); break; }
-                        hipFree(old);
-                    }
-                    ws.order = nullptr; ws.logp = nullptr; ws.target = nullptr; ws.gallow = nullptr; ws.capT = 0;
-                    ws.conf = nullptr; ws.order0 = nullptr; ws.target0 = nullptr; ws.gallow0 = nullptr;
-                    // a captured graph holds the old pointers
-                    ln.drop_graphs();
-                }
-                HD_TRY(dalloc(ws, &ws.order, need));
-                HD_TRY(dalloc(ws, &ws.logp, need));
-                HD_TRY(dalloc(ws, &ws.target, need));
-                HD_TRY(dalloc(ws, &ws.gallow, need));
-                HD_TRY(dalloc(ws, &ws.conf, need));
-                HD_TRY(dalloc(ws, &ws.order0, need));
-                HD_TRY(dalloc(ws, &ws.target0, need));
-                HD_TRY(dalloc(ws, &ws.gallow0, need));
-                ws.capT = (int)need;
-            }
-            if (guide && guide->has_bias && need * 22 > ws.gbias_cap) {
-                if (ws.gbias) {                 // as above: a captured guided graph holds the old pointer
-                    HIP_TRY(hipStreamSynchronize(ln.stream));
-                    for (void* old : {(void*)ws.gbias, (void*)ws.gbias0}) {
-                        for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
-                            if (*it == old) { ws.owned.erase(it); break; }
-                        hipFree(old);
-                    }
-                    ws.gbias = nullptr; ws.gbias0 = nullptr; ws.gbias_cap = 0;
-                    ln.drop_graphs();
-                }
-                HD_TRY(dalloc(ws, &ws.gbias, need * 22));
-                HD_TRY(dalloc(ws, &ws.gbias0, need * 22));
-                ws.gbias_cap = need * 22;
-            }
-        }
-        if (W > 0) {
-            if ((size_t)Bl > ws.beam_capB || need_T(Bl, Tmax) > ws.beam_capT) {
-                HIP_TRY(hipStreamSynchronize(ln.stream));
-                for (void* old : {(void*)ws.bscore, (void*)ws.bcand, (void*)ws.blp, (void*)ws.bparent}) {
-                    if (!old) continue;
-                    for (auto it = ws.owned.begin(); it != ws.owned.end(); ++it)
-                        if (*it == old) { ws.owned.erase(it); break; }
-                    hipFree(old);
-                }
-                ws.bscore = nullptr; ws.bcand = nullptr; ws.blp = nullptr; ws.bparent = nullptr; ws.beam_capB = 0; ws.beam_capT = 0;
-                ln.drop_graphs();                    // a captured beam step holds the old pointers
-                HD_TRY(dalloc(ws, &ws.bscore, (size_t)Bl));
-                HD_TRY(dalloc(ws, &ws.bcand, (size_t)Bl * 22));
-                HD_TRY(dalloc(ws, &ws.blp, (size_t)Bl * 22));
-                HD_TRY(dalloc(ws, &ws.bparent, need_T(Bl, Tmax)));
-                ws.beam_capB = (size_t)Bl; ws.beam_capT = need_T(Bl, Tmax);
-            }
-            HIP_TRY(hipMemcpyAsync(ws.bscore, m->beam_score0.data() + off, (size_t)Bl * sizeof(float), hipMemcpyHostToDevice, ln.stream));
-            HIP_TRY(hipMemsetAsync(ws.bparent, 0, need_T(Bl, Tmax) * sizeof(int32_t), ln.stream));
-            HIP_TRY(hipMemsetAsync(ws.bcand, 0, (size_t)Bl * 22 * sizeof(float), ln.stream));
-        }
-        if (guide && Tmax > 0) {
-            HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
-            if (guide->has_bias)
-                HIP_TRY(hipMemcpyAsync(ws.gbias, gbias.data() + (size_t)off * Tmax * 22, (size_t)Bl * Tmax * 22 * sizeof(float), hipMemcpyHostToDevice, ln.stream));
-        }
-        if (Tmax > 0) HIP_TRY(hipMemcpyAsync(ws.order, order + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
-        HIP_TRY(hipMemcpyAsync(ws.T, T + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
-        if (m->s_mode != DRAW_SAMPLE && Tmax > 0) {
-            HIP_TRY(hipMemsetAsync(ws.logp, 0, (size_t)Bl * Tmax * sizeof(float), ln.stream));
-            if (score) HIP_TRY(hipMemcpyAsync(ws.target, target.data() + (size_t)off * Tmax, (size_t)Bl * Tmax * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
-        }
-        if (confident && Tmax > 0) {                 // what slot_select_k permutes, as uploaded: hd_sample_restart starts from the caller's list again
-            const size_t nT = (size_t)Bl * Tmax;
-            HIP_TRY(hipMemcpyAsync(ws.order0, ws.order, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
-            if (score) HIP_TRY(hipMemcpyAsync(ws.target0, ws.target, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
-            if (guide) HIP_TRY(hipMemcpyAsync(ws.gallow0, ws.gallow, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
-            if (guide && guide->has_bias) HIP_TRY(hipMemcpyAsync(ws.gbias0, ws.gbias, nT * 22 * sizeof(float), hipMemcpyDeviceToDevice, ln.stream));
-        }
-        if (l == 0 && q_noise && Tmax > 0) {
-            const size_t n = (size_t)Tmax * B * 22;
-            if (n > m->qnoise_cap) {
-                for (auto& o : m->lane) if (o.stream) HIP_TRY(hipStreamSynchronize(o.stream));
-                if (m->qnoise) { hipFree(m->qnoise); m->qnoise = nullptr; m->qnoise_cap = 0; }
-                HIP_TRY(hipMalloc(&m->qnoise, n * sizeof(float)));
-                m->qnoise_cap = n;
-            }
-            HIP_TRY(hipMemcpyAsync(m->qnoise, q_noise, n * sizeof(float), hipMemcpyHostToDevice, ln.stream));
-        }
-        if (dm == DROP_INJECT && Tmax > 0) {
-            const size_t ne = (size_t)Tmax * m->cfg.n_encoder_layers * B * m->L * m->d, nc = (size_t)Tmax * m->cfg.dual_layers * B * m->L * m->D;
-            HD_TRY(ensure_buf(m, &ws.enc_masks, &ws.enc_cap, ne));
-            HD_TRY(ensure_buf(m, &ws.conv_masks, &ws.conv_cap, nc));
-            HIP_TRY(hipMemcpyAsync(ws.enc_masks, enc_masks, ne, hipMemcpyHostToDevice, ln.stream));
-            HIP_TRY(hipMemcpyAsync(ws.conv_masks, conv_masks, nc, hipMemcpyHostToDevice, ln.stream));
-        }
-        HIP_TRY(hipMemcpyAsync(ws.tokens0, ws.tokens, (size_t)Bl * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
-        HD_TRY(set_run_state(m, seed, row0 + (uint64_t)off, 0));
-        HD_TRY(static_branch(m, sg));
+    if (m->nseg > 1) {                // chain[0:B] heavy ids, chain[B:2B] light ids -> this lane's [heavy | light]
+        chain_l.assign((size_t)2 * Bl, 0);
+        for (int b = 0; b < Bl; ++b) { chain_l[b] = in.chain[off + b]; chain_l[Bl + b] = in.chain[B + off + b]; }
     }
+    HD_TRY(upload_common(m, in.tokens + (size_t)off * m->L, in.region + (size_t)off * m->L, m->nseg > 1 ? chain_l.data() : nullptr, Bl));
+    HIP_TRY(hipStreamSynchronize(ln.stream));              // chain_l goes with this call
+    const size_t need = (size_t)Bl * (Tmax > 0 ? Tmax : 1), nT = (size_t)Bl * Tmax;
+    if (need > (size_t)ws.capT) {
+        ws.capT = 0;
+        HD_TRY(regrow(ln, [&](auto f) { return bufs_per_step(ws, need, f); }));
+        ws.capT = (int)need;
+    }
+    if (biased && need * 22 > ws.gbias_cap) {
+        ws.gbias_cap = 0;
+        HD_TRY(regrow(ln, [&](auto f) { return bufs_bias(ws, need * 22, f); }));
+        ws.gbias_cap = need * 22;
+    }
+    if (o.W > 0) {
+        if ((size_t)Bl > ws.beam_capB || need > ws.beam_capT) {
+            ws.beam_capB = 0; ws.beam_capT = 0;
+            HD_TRY(regrow(ln, [&](auto f) { return bufs_beam(ws, (size_t)Bl, need, f); }));
+            ws.beam_capB = (size_t)Bl; ws.beam_capT = need;
+        }
+        HIP_TRY(hipMemcpyAsync(ws.bscore, m->beam_score0.data() + off, (size_t)Bl * sizeof(float), hipMemcpyHostToDevice, ln.stream));
+        HIP_TRY(hipMemsetAsync(ws.bparent, 0, need * sizeof(int32_t), ln.stream));
+        HIP_TRY(hipMemsetAsync(ws.bcand, 0, (size_t)Bl * 22 * sizeof(float), ln.stream));
+    }
+    if (guided && Tmax > 0) {
+        HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, nT * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
+        if (biased) HIP_TRY(hipMemcpyAsync(ws.gbias, gbias.data() + (size_t)off * Tmax * 22, nT * 22 * sizeof(float), hipMemcpyHostToDevice, ln.stream));
+    }
+    if (Tmax > 0) HIP_TRY(hipMemcpyAsync(ws.order, in.order + (size_t)off * Tmax, nT * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+    HIP_TRY(hipMemcpyAsync(ws.T, in.T + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+    if (o.mode != DRAW_SAMPLE && Tmax > 0) {
+        HIP_TRY(hipMemsetAsync(ws.logp, 0, nT * sizeof(float), ln.stream));
+        if (in.score) HIP_TRY(hipMemcpyAsync(ws.target, target.data() + (size_t)off * Tmax, nT * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+    }
+    if (o.policy == HD_SLOTS_CONFIDENT && Tmax > 0) {    // what slot_select_k permutes, as uploaded: hd_sample_restart starts from the caller's list again
+        HIP_TRY(hipMemcpyAsync(ws.order0, ws.order, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+        if (in.score) HIP_TRY(hipMemcpyAsync(ws.target0, ws.target, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+        if (guided) HIP_TRY(hipMemcpyAsync(ws.gallow0, ws.gallow, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
+        if (biased) HIP_TRY(hipMemcpyAsync(ws.gbias0, ws.gbias, nT * 22 * sizeof(float), hipMemcpyDeviceToDevice, ln.stream));
+    }
+    if (m->cl == 0 && in.q_noise && Tmax > 0) {          // the noise of the whole batch, once
+        const size_t n = (size_t)Tmax * B * 22;
+        if (n > m->qnoise_cap) {
+            for (auto& other : m->lane) if (other.stream) HIP_TRY(hipStreamSynchronize(other.stream));
+            if (m->qnoise) { hipFree(m->qnoise); m->qnoise = nullptr; m->qnoise_cap = 0; }
+            HIP_TRY(hipMalloc(&m->qnoise, n * sizeof(float)));
+            m->qnoise_cap = n;
+        }
+        HIP_TRY(hipMemcpyAsync(m->qnoise, in.q_noise, n * sizeof(float), hipMemcpyHostToDevice, ln.stream));
+    }
+    if (dm == DROP_INJECT && Tmax > 0) {
+        const size_t ne = (size_t)Tmax * m->cfg.n_encoder_layers * B * m->L * m->d, nc = (size_t)Tmax * m->cfg.dual_layers * B * m->L * m->D;
+        HD_TRY(ensure_buf(m, &ws.enc_masks, &ws.enc_cap, ne));
+        HD_TRY(ensure_buf(m, &ws.conv_masks, &ws.conv_cap, nc));
+        HIP_TRY(hipMemcpyAsync(ws.enc_masks, in.enc_masks, ne, hipMemcpyHostToDevice, ln.stream));
+        HIP_TRY(hipMemcpyAsync(ws.conv_masks, in.conv_masks, nc, hipMemcpyHostToDevice, ln.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(ws.tokens0, ws.tokens, (size_t)Bl * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+    HD_TRY(set_run_state(m, in.seed, in.row0 + (uint64_t)off, 0));
+    return static_branch(m, sg);
+}
+
+// `o` and `guide`: what take_pending took.  The session's options are worked out on the local copy and reach m->s only with success.
+static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel::Guide& guide) {
+    if (!m || !in.tokens || !in.region || !in.T || (in.Tmax > 0 && !in.order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
+    if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
+    const int B = in.B, Tmax = in.Tmax;
+    if (B < 0 || Tmax < 0) return fail(HD_ERR_INVALID, "hd_sample_begin: B = %d, Tmax = %d", B, Tmax);
+    HIP_TRY(hipSetDevice(m->device));
+    m->sB = B; m->sTmax = Tmax; m->sflags = in.flags; m->s_has_q = in.q_noise != nullptr; m->timed = false; m->last_steps = 0;
+    m->s_seed = in.seed; m->s_steps = 0; m->s_dirty = false;
+    m->nlanes = 1; m->cl = 0;
+    m->logp_ready = false;
+    m->order_ready = false;
+    o.mode = in.score ? DRAW_SCORE : ((in.flags & HD_RECORD_LOGP) || o.W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
+    // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
+    // bias, temperature 1), under which g_j == logit_j bit for bit
+    if (o.trunc && o.guide == GUIDE_NONE) { o.guide = GUIDE_ALLOW; o.temp = 1.f; guide = HdModel::Guide(); guide.B = B; }
+    HD_TRY(check_options(m, in, o, guide));
+    if (B == 0) {                                    // no row: nothing to guide or truncate
+        o.guide = GUIDE_NONE; o.temp = 1.f; o.trunc = false; o.tr = TruncP{0, 1.f, 0.f};
+        m->s = o; m->in_session = true;
+        return HD_OK;
+    }
+    HD_TRY(validate_inputs(m, in.tokens, in.region, in.chain, B));
+    HD_TRY(check_orders(m, in, o));
+    std::vector<int32_t> masked, target;
+    if (in.score) { HD_TRY(score_targets(m, in, masked, target)); in.tokens = masked.data(); }
+    std::vector<uint32_t> gallow;
+    std::vector<float> gbias;
+    if (o.guide != GUIDE_NONE) HD_TRY(gather_guide(m, in, o, guide, target, gallow, gbias));
+    const int dm = drop_mode_of(m, in.flags);
+    if (dm == DROP_INJECT && (!in.enc_masks || !in.conv_masks)) return fail(HD_ERR_INVALID, "hd_sample_begin: HD_DROPOUT_INJECT needs masks");
+    split_lanes(m, in, o, dm);
+    if (o.W > 0) {
+        m->beam_score0.assign((size_t)B, -INFINITY);
+        for (int b = 0; b < B; b += o.W) m->beam_score0[b] = 0.f;
+    }
+    for (m->cl = 0; m->cl < m->nlanes; ++m->cl) HD_TRY(lane_begin(m, in, o, dm, target, gallow, gbias));
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
     m->cl = 0;
-    m->s_row0 = row0;
-    if (guide) { m->s_guide = guide->has_bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW; m->s_temp = guide->temperature; }
-    m->sK = K;
-    m->s_policy = policy;
-    m->sW = W;
-    if (trunc) { m->s_trunc = true; m->s_tr = *trunc; }
+    m->s_row0 = in.row0;
+    m->s = o;
     m->in_session = true;
     return HD_OK;
 }
 
-// The guide hd_set_guide left is taken by the begin that follows, whatever becomes of that begin.
-static bool take_guide(HdModel* m, HdModel::Guide* g) {
-    if (!m || !m->guide_pending) return false;
-    *g = std::move(m->guide);
+// What the hd_set_* functions left is taken by the begin that follows, whatever becomes of that begin (hd_forward neither uses nor clears it).
+static SessionOpts take_pending(HdModel* m, HdModel::Guide* guide) {
+    if (!m) return SessionOpts();
+    const SessionOpts o = m->pending;
+    *guide = std::move(m->guide);
+    m->pending = SessionOpts();
     m->guide = HdModel::Guide();
-    m->guide_pending = false;
-    return true;
+    return o;
 }
 
-// So is the block size hd_set_slots_per_step left.
-static int take_slots_per_step(HdModel* m) {
-    if (!m) return 1;
-    const int k = m->k_next;
-    m->k_next = 1;
-    return k;
-}
-
-// And the slot policy hd_set_slot_policy left.
-static int take_slot_policy(HdModel* m) {
-    if (!m) return HD_SLOTS_GIVEN;
-    const int p = m->policy_next;
-    m->policy_next = HD_SLOTS_GIVEN;
-    return p;
-}
-
-// And the beam width hd_set_beam left.
-static int take_beam(HdModel* m) {
-    if (!m) return 0;
-    const int w = m->beam_next;
-    m->beam_next = 0;
-    return w;
-}
-
-// And the truncation hd_set_truncation left.
-static bool take_truncation(HdModel* m, TruncP* tr) {
-    if (!m || !m->trunc_pending) return false;
-    *tr = m->trunc_next;
-    m->trunc_next = TruncP{0, 1.f, 0.f};
-    m->trunc_pending = false;
-    return true;
+static HdStatus begin_session(HdModel* m, const BeginIn& in) {
+    HdModel::Guide guide;
+    const SessionOpts o = take_pending(m, &guide);
+    const bool was_open = m && m->in_session;
+    const HdStatus s = sample_begin_impl(m, in, o, guide);
+    if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
+        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false;
+        m->s = SessionOpts();                    // (hd_sample_logp / hd_beam_state of an earlier session then answer as for a plain one)
+    }
+    return s;
 }
 
 extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                     const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                     uint64_t seed, uint64_t row0, const float* q_noise,
                                     const uint8_t* enc_masks, const uint8_t* conv_masks) {
-    HdModel::Guide g;
-    const bool guided = take_guide(m, &g);
-    const bool was_open = m && m->in_session;
-    const int K = take_slots_per_step(m);
-    const int policy = take_slot_policy(m);
-    TruncP tr;
-    const bool truncated = take_truncation(m, &tr);
-    const int W = take_beam(m);
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false, guided ? &g : nullptr, K, policy,
-                                         truncated ? &tr : nullptr, W);
-    if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
-        m->s_policy = HD_SLOTS_GIVEN;
-        m->s_trunc = false;
-        m->sW = 0;
-    }
-    return s;
+    return begin_session(m, BeginIn{tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks, false});
 }
 
 // A teacher-forced recording session (include/hudiff_hip.h "likelihood scoring"): hd_sample_begin on the library's masked copy of the
@@ -2344,23 +2292,7 @@ extern "C" HdStatus hd_sample_begin(HdModel* m, const int32_t* tokens, const int
 extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                                    const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                                    uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks) {
-    HdModel::Guide g;
-    const bool guided = take_guide(m, &g);
-    const bool was_open = m && m->in_session;
-    const int K = take_slots_per_step(m);
-    const int policy = take_slot_policy(m);
-    TruncP tr;
-    const bool truncated = take_truncation(m, &tr);
-    const int W = take_beam(m);
-    const HdStatus s = sample_begin_impl(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true, guided ? &g : nullptr, K, policy,
-                                         truncated ? &tr : nullptr, W);
-    if (s != HD_OK && m && !was_open) {
-        m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false; m->s_mode = DRAW_SAMPLE; m->s_guide = GUIDE_NONE; m->s_temp = 1.f; m->sK = 1;
-        m->s_policy = HD_SLOTS_GIVEN;
-        m->s_trunc = false;
-        m->sW = 0;
-    }
-    return s;
+    return begin_session(m, BeginIn{tokens, region, chain, order, T, B, Tmax, flags, seed, row0, nullptr, enc_masks, conv_masks, true});
 }
 
 extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
@@ -2375,17 +2307,17 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         m->cl = l;
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
-        if (m->s_mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
-        if (m->sW > 0) {                             // beam search: only the first row of every group is live again
+        if (m->s.mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
+        if (m->s.W > 0) {                             // beam search: only the first row of every group is live again
             HIP_TRY(hipMemcpyAsync(ln.ws.bscore, m->beam_score0.data() + ln.row_off, (size_t)ln.B * sizeof(float), hipMemcpyHostToDevice, ln.stream));
             HIP_TRY(hipMemsetAsync(ln.ws.bparent, 0, (size_t)ln.B * (m->sTmax > 0 ? m->sTmax : 1) * sizeof(int32_t), ln.stream));
         }
-        if (m->s_policy == HD_SLOTS_CONFIDENT && m->sTmax > 0) {      // back to the caller's candidate list
+        if (m->s.policy == HD_SLOTS_CONFIDENT && m->sTmax > 0) {      // back to the caller's candidate list
             const size_t nT = (size_t)ln.B * m->sTmax;
             HIP_TRY(hipMemcpyAsync(ln.ws.order, ln.ws.order0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
-            if (m->s_mode == DRAW_SCORE) HIP_TRY(hipMemcpyAsync(ln.ws.target, ln.ws.target0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
-            if (m->s_guide != GUIDE_NONE) HIP_TRY(hipMemcpyAsync(ln.ws.gallow, ln.ws.gallow0, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
-            if (m->s_guide == GUIDE_ALLOW_BIAS) HIP_TRY(hipMemcpyAsync(ln.ws.gbias, ln.ws.gbias0, nT * 22 * sizeof(float), hipMemcpyDeviceToDevice, ln.stream));
+            if (m->s.mode == DRAW_SCORE) HIP_TRY(hipMemcpyAsync(ln.ws.target, ln.ws.target0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (m->s.guide != GUIDE_NONE) HIP_TRY(hipMemcpyAsync(ln.ws.gallow, ln.ws.gallow0, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
+            if (m->s.guide == GUIDE_ALLOW_BIAS) HIP_TRY(hipMemcpyAsync(ln.ws.gbias, ln.ws.gbias0, nT * 22 * sizeof(float), hipMemcpyDeviceToDevice, ln.stream));
         }
         HD_TRY(set_run_state(m, seed, m->s_row0 + (uint64_t)ln.row_off, 0));
     }
@@ -2393,10 +2325,26 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
     return HD_OK;
 }
 
+// The key of the step the open session would capture on lane ln.  Fields the session does not use are normalised, so that two sessions
+// whose launches are equal have equal keys.  Floats are compared by value.
+static StepKey step_key(const HdModel* m, const HdModel::Lane& ln) {
+    StepKey k;
+    k.captured = true;
+    k.B = ln.B; k.no_prune = m->sflags & HD_NO_PRUNE; k.drop = drop_mode_of(m, m->sflags); k.Tmax = m->sTmax;
+    k.has_q = m->s_has_q; k.qptr = m->s_has_q ? m->qnoise : nullptr; k.qB = m->sB; k.qoff = ln.row_off;
+    k.kernels = kernel_set(m);
+    k.o = m->s;
+    if (k.o.guide == GUIDE_NONE) k.o.temp = 1.f;
+    if (!k.o.trunc) k.o.tr = TruncP{0, 1.f, 0.f};
+    k.gallow = k.o.guide != GUIDE_NONE ? ln.ws.gallow : nullptr;
+    k.gbias = k.o.guide == GUIDE_ALLOW_BIAS ? ln.ws.gbias : nullptr;
+    return k;
+}
+
 extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_run: no open session");
     if (t0 < 0 || t1 < t0 || t1 > m->sTmax) return fail(HD_ERR_INVALID, "hd_sample_run: steps [%d,%d) outside [0,%d]", t0, t1, m->sTmax);
-    const int K = m->sK;
+    const int K = m->s.K;
     if (K > 1 && (t0 % K != 0 || (t1 % K != 0 && t1 != m->sTmax)))
         return fail(HD_ERR_INVALID, "hd_sample_run: steps [%d,%d) of a session with %d slots per step: t0 must be a multiple of %d, t1 a multiple or Tmax = %d",
                     t0, t1, K, K, m->sTmax);
@@ -2412,13 +2360,8 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
         const Segs sg = make_segs(m, ln.B);
         hipLaunchKernelGGL(set_step_k, dim3(1), dim3(1), 0, ln.stream, ln.rs, (uint32_t)t0);
         if (!use_graph) continue;
-        const uint32_t gflags = m->sflags & HD_NO_PRUNE;
-        if (!ln.graph_exec || ln.graph_B != ln.B || ln.graph_flags != gflags || ln.graph_drop != dm || ln.graph_q != m->s_has_q ||
-            ln.graph_Tmax != m->sTmax || ln.graph_qB != m->sB || ln.graph_qoff != ln.row_off ||
-            ln.graph_qptr != (m->s_has_q ? m->qnoise : nullptr) || ln.graph_x3 != kernel_set(m) || ln.graph_mode != m->s_mode || ln.graph_K != K || ln.graph_policy != m->s_policy || ln.graph_W != m->sW ||
-            ln.graph_guide != m->s_guide || (m->s_guide != GUIDE_NONE && (ln.graph_temp != m->s_temp || ln.graph_gallow != ln.ws.gallow)) ||
-            (m->s_guide == GUIDE_ALLOW_BIAS && ln.graph_gbias != ln.ws.gbias) || ln.graph_trunc != m->s_trunc ||
-            (m->s_trunc && (ln.graph_tr.top_k != m->s_tr.top_k || ln.graph_tr.top_p != m->s_tr.top_p || ln.graph_tr.min_p != m->s_tr.min_p))) {
+        const StepKey key = step_key(m, ln);
+        if (!(ln.graph_key == key)) {
             ln.drop_graphs();
             HIP_TRY(hipStreamSynchronize(ln.stream));
             HIP_TRY(hipStreamBeginCapture(ln.stream, hipStreamCaptureModeThreadLocal));
@@ -2427,11 +2370,7 @@ extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
             if (s != HD_OK) { m->cl = 0; return s; }
             if (e != hipSuccess) { m->cl = 0; return fail(HD_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e)); }
             HIP_TRY(hipGraphInstantiate(&ln.graph_exec, ln.graph, nullptr, nullptr, 0));
-            ln.graph_B = ln.B; ln.graph_flags = gflags; ln.graph_drop = dm; ln.graph_q = m->s_has_q; ln.graph_Tmax = m->sTmax;
-            ln.graph_qB = m->sB; ln.graph_qoff = ln.row_off; ln.graph_qptr = m->s_has_q ? m->qnoise : nullptr;
-            ln.graph_x3 = kernel_set(m); ln.graph_mode = m->s_mode; ln.graph_K = K; ln.graph_policy = m->s_policy; ln.graph_W = m->sW;
-            ln.graph_guide = m->s_guide; ln.graph_temp = m->s_temp; ln.graph_gallow = ln.ws.gallow; ln.graph_gbias = ln.ws.gbias;
-            ln.graph_trunc = m->s_trunc; ln.graph_tr = m->s_tr;
+            ln.graph_key = key;
         }
     }
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipEventRecord(m->lane[l].ev0, m->lane[l].stream));
@@ -2534,7 +2473,7 @@ static HdStatus sample_end_impl(HdModel* m, int32_t* tokens, bool* numeric) {
 
 extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_end: no open session");
-    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s_mode != DRAW_SAMPLE; m->order_ready = true; return HD_OK; }
+    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s.mode != DRAW_SAMPLE; m->order_ready = true; return HD_OK; }
     if (!tokens) { m->in_session = false; return fail(HD_ERR_INVALID, "hd_sample_end: null tokens"); }
     bool numeric = false;
     const HdStatus s = sample_end_impl(m, tokens, &numeric);
@@ -2542,7 +2481,7 @@ extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     m->s_dirty = false;
     m->cl = 0;
     if (s != HD_OK) return s;
-    m->logp_ready = m->s_mode != DRAW_SAMPLE;        // hd_sample_logp stays legal until the next begin / hd_forward
+    m->logp_ready = m->s.mode != DRAW_SAMPLE;        // hd_sample_logp stays legal until the next begin / hd_forward
     m->order_ready = true;                           // and so does hd_sample_order
     if (numeric)
         return fail(HD_ERR_NUMERIC, "hd_sample: non-finite logits (NaN / inf) at some denoiser step -- weights or inputs out of range; "
@@ -2616,8 +2555,8 @@ extern "C" HdStatus hd_sample(HdModel* m, int32_t* tokens, const int32_t* region
     HD_TRY(hd_sample_begin(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks));
     int tmax_eff = 0;
     for (int b = 0; b < B; ++b) tmax_eff = T[b] > tmax_eff ? T[b] : tmax_eff;
-    if (m->sK > 1) {                                 // whole groups (or up to Tmax): what hd_sample_run takes in a block session
-        tmax_eff = (tmax_eff + m->sK - 1) / m->sK * m->sK;
+    if (m->s.K > 1) {                                 // whole groups (or up to Tmax): what hd_sample_run takes in a block session
+        tmax_eff = (tmax_eff + m->s.K - 1) / m->s.K * m->s.K;
         if (tmax_eff > Tmax) tmax_eff = Tmax;
     }
     HdStatus s = hd_sample_run(m, 0, tmax_eff);
@@ -2625,9 +2564,20 @@ extern "C" HdStatus hd_sample(HdModel* m, int32_t* tokens, const int32_t* region
     return hd_sample_end(m, tokens);
 }
 
+// The shared tail of the read-backs (hd_sample_logp, hd_beam_state, hd_sample_order), behind their copies: inside a session the guards
+// are looked at (or, with no step run, the lanes are waited for) and values of steps a guard fired in are refused; after the end the
+// lanes are only waited for.
+static HdStatus readback_done(HdModel* m, const char* fn, const char* what) {
+    if (m->in_session && m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
+    else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
+    if (m->in_session && m->s_dirty)
+        return fail(HD_ERR_STATE, "%s: a guard of the split-precision kernels fired during these steps; their %s invalid (hd_sample_end repeats the sample)", fn, what);
+    return HD_OK;
+}
+
 extern "C" HdStatus hd_sample_logp(HdModel* m, float* logp) {
     if (!m || (!m->in_session && !m->logp_ready)) return fail(HD_ERR_STATE, "hd_sample_logp: no recording session (open, or ended and not yet replaced)");
-    if (m->s_mode == DRAW_SAMPLE) return fail(HD_ERR_STATE, "hd_sample_logp: the session does not record (HD_RECORD_LOGP / hd_score_begin)");
+    if (m->s.mode == DRAW_SAMPLE) return fail(HD_ERR_STATE, "hd_sample_logp: the session does not record (HD_RECORD_LOGP / hd_score_begin)");
     if (m->sB == 0 || m->sTmax == 0) return HD_OK;
     if (!logp) return fail(HD_ERR_INVALID, "hd_sample_logp: null logp");
     HIP_TRY(hipSetDevice(m->device));
@@ -2635,21 +2585,13 @@ extern "C" HdStatus hd_sample_logp(HdModel* m, float* logp) {
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(logp + (size_t)ln.row_off * m->sTmax, ln.ws.logp, (size_t)ln.B * m->sTmax * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
     }
-    if (m->in_session) {
-        if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
-        else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
-        if (m->s_dirty) return fail(HD_ERR_STATE, "hd_sample_logp: a guard of the split-precision kernels fired during these steps; their values "
-                                                   "are invalid (hd_sample_end repeats the sample)");
-    } else {
-        for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
-    }
-    return HD_OK;
+    return readback_done(m, "hd_sample_logp", "values are");
 }
 
 // include/hudiff_hip.h "beam search": score, parent and the candidate table of the last position run.
 extern "C" HdStatus hd_beam_state(HdModel* m, float* score, int32_t* parent, float* cand) {
     if (!m || (!m->in_session && !m->logp_ready)) return fail(HD_ERR_STATE, "hd_beam_state: no beam session (open, or ended and not yet replaced)");
-    if (m->sW <= 0) return fail(HD_ERR_STATE, "hd_beam_state: the session is not a beam session (hd_set_beam)");
+    if (m->s.W <= 0) return fail(HD_ERR_STATE, "hd_beam_state: the session is not a beam session (hd_set_beam)");
     if (m->sB == 0) return HD_OK;
     HIP_TRY(hipSetDevice(m->device));
     for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
@@ -2659,15 +2601,7 @@ extern "C" HdStatus hd_beam_state(HdModel* m, float* score, int32_t* parent, flo
             HIP_TRY(hipMemcpyAsync(parent + (size_t)ln.row_off * m->sTmax, ln.ws.bparent, (size_t)ln.B * m->sTmax * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
         if (cand) HIP_TRY(hipMemcpyAsync(cand + (size_t)ln.row_off * 22, ln.ws.bcand, (size_t)ln.B * 22 * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
     }
-    if (m->in_session) {
-        if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
-        else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
-        if (m->s_dirty) return fail(HD_ERR_STATE, "hd_beam_state: a guard of the split-precision kernels fired during these steps; their values "
-                                                   "are invalid (hd_sample_end repeats the sample)");
-    } else {
-        for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
-    }
-    return HD_OK;
+    return readback_done(m, "hd_beam_state", "values are");
 }
 
 // include/hudiff_hip.h "slot policy": the order the session has taken so far (a given-order session: the order it was given).
@@ -2680,15 +2614,7 @@ extern "C" HdStatus hd_sample_order(HdModel* m, int32_t* order) {
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(order + (size_t)ln.row_off * m->sTmax, ln.ws.order, (size_t)ln.B * m->sTmax * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
     }
-    if (m->in_session) {
-        if (m->s_steps > 0) HD_TRY(check_guards(m, m->nlanes, nullptr));
-        else for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
-        if (m->s_dirty) return fail(HD_ERR_STATE, "hd_sample_order: a guard of the split-precision kernels fired during these steps; their order "
-                                                   "is invalid (hd_sample_end repeats the sample)");
-    } else {
-        for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
-    }
-    return HD_OK;
+    return readback_done(m, "hd_sample_order", "order is");
 }
 
 extern "C" HdStatus hd_score(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,

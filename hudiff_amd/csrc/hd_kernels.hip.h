@@ -2641,102 +2641,30 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     }
 }
 
-// advance != 0: the last workgroup to finish moves rs->step on (every thread of the grid has read it by then), which saves the
-// one-thread launch per step that advance_step_k was.
-// logp / target: [B, Tmax] of the lane (row b at step t), used by the recording and the teacher-forced kernel below only.
+// The draw stage of a session, sample_step_k<MODE, GUIDED, TRUNC>: ONE forward serves the K = gridDim.y order positions
+// t = step + j, j = 0 .. K-1, and workgroup (b, j) runs sample_row for row b at position t on the hidden row of slot order[b, t].  Noise,
+// guide, target and logp are those of position t.
+//   K == 1  the one-slot step.  compact != 0: Hm is [B, D] and holds only the visited row of each sequence (pruned last block).
+//   K > 1   block decoding (hd_set_slots_per_step): Hm is the FULL hidden buffer of this forward, [rows, D]; the host passes compact
+//           only with K == 1.  It has checked that no row repeats a slot inside one group, so no two workgroups write one token.
+// The last workgroup of the whole grid to finish stores step + K (every workgroup has read `step` before it increments `done`), which
+// saves the one-thread launch per step that advance_step_k was.
+// logp / target: [B, Tmax] of the lane (row b at step t); read and written by the recording and the teacher-forced modes only.
+// Nine instantiations: three modes x {plain, guided, guided + truncation}.  The guide argument is GuideP when GUIDED, GuideTP (the three
+// cut parameters behind the guide) when TRUNC, and an empty struct otherwise.
 constexpr int SS_WAVES = 16;
-template <int MODE, bool GUIDED = false, bool TRUNC = false>
-__device__ __forceinline__ void sample_step_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
-                                                 const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
-                                                 const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                 RunState* __restrict__ rs, const Segs& sg, int compact, int advance,
-                                                 float* __restrict__ logp, const int32_t* __restrict__ target,
-                                                 [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f},
-                                                 [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
-    __shared__ float lg[32];
-    const int b = blockIdx.x;
-    const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((int)t < T[b]) {
-        const int slot = order[(long)b * Tmax + t];
-        // compact: Hm is [B, D] holding only the visited row of each sequence (pruned last block)
-        const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
-        if constexpr (GUIDED) {
-            const long bt = (long)b * Tmax + t;
-            sample_row<SS_WAVES, MODE, true, TRUNC>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
-                                                    MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
-                                                    g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr);
-        } else if constexpr (MODE == DRAW_SAMPLE)
-            sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
-        else
-            sample_row<SS_WAVES, MODE>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg, logp + (long)b * Tmax + t,
-                                       MODE == DRAW_SCORE ? target[(long)b * Tmax + t] : 0);
-    } else {
-        __syncthreads();                                 // (sample_row has one: every wave has read the step before thread 0 goes on)
-    }
-    if (advance && threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(&rs->done, 1u) == gridDim.x - 1) {
-            __hip_atomic_store(&rs->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&rs->step, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
+struct NoGuide {};
+template <bool GUIDED, bool TRUNC> using DrawGuideArg = std::conditional_t<GUIDED, GuideArg<TRUNC>, NoGuide>;
+template <int MODE, bool GUIDED, bool TRUNC>
 __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __restrict__ Hm, int D, HeadW w,
                                                      int32_t* __restrict__ tokens,
                                                      const int32_t* __restrict__ order,
                                                      const int32_t* __restrict__ T, int Tmax,
                                                      const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance) {
-    sample_step_body<DRAW_SAMPLE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, nullptr, nullptr);
-}
-// The step of a recording (HD_RECORD_LOGP) or a teacher-forced (hd_score_begin) session: as sample_step_k, and logp[b, t] is written
-// for every row with t < T[b].
-template <int MODE>
-__global__ void __launch_bounds__(64 * SS_WAVES) sample_step_logp_k(const float* __restrict__ Hm, int D, HeadW w,
-                                                     int32_t* __restrict__ tokens,
-                                                     const int32_t* __restrict__ order,
-                                                     const int32_t* __restrict__ T, int Tmax,
-                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance,
-                                                     float* __restrict__ logp, const int32_t* __restrict__ target) {
-    static_assert(MODE == DRAW_RECORD || MODE == DRAW_SCORE, "the plain draw is sample_step_k");
-    sample_step_body<MODE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target);
-}
-
-// The step of a GUIDED session (hd_set_guide) in any of the three draw modes; logp / target may be nullptr in DRAW_SAMPLE.  Sessions
-// without a guide never launch it.  TRUNC: the step of a truncated session (hd_set_truncation), guided or not; the argument then carries
-// the three cut parameters behind the guide, and the instantiations without it are what they were.
-template <int MODE, bool TRUNC = false>
-__global__ void __launch_bounds__(64 * SS_WAVES) sample_step_guided_k(const float* __restrict__ Hm, int D, HeadW w,
-                                                     int32_t* __restrict__ tokens,
-                                                     const int32_t* __restrict__ order,
-                                                     const int32_t* __restrict__ T, int Tmax,
-                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg, int compact, int advance,
-                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideArg<TRUNC> g) {
-    if constexpr (TRUNC)
-        sample_step_body<MODE, true, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target,
-                                           g.g, g.tr);
-    else
-        sample_step_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, compact, advance, logp, target, g);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Block decoding (hd_set_slots_per_step, K = gridDim.y > 1): ONE forward serves the K order positions t = step + j, j = 0 .. K-1.
-// Workgroup (b, j) does what the one-slot kernels above do for row b at position t -- the same sample_row, so the same arithmetic --
-// on the row of slot order[b, t] in the FULL hidden buffer of this forward (Hm is [rows, D]; there is no compact form).  Noise, guide,
-// target and logp are those of position t.  The host has checked that no row repeats a slot inside one group, so no two workgroups
-// write one token.  The last workgroup of the whole grid to finish stores step + K; every workgroup has read `step` before it
-// increments `done`.
-// ------------------------------------------------------------------------------------------------
-template <int MODE, bool GUIDED = false, bool TRUNC = false>
-__device__ __forceinline__ void sample_block_body(const float* __restrict__ Hm, int D, const HeadW& w, int32_t* __restrict__ tokens,
-                                                  const int32_t* __restrict__ order, const int32_t* __restrict__ T, int Tmax,
-                                                  const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                  RunState* __restrict__ rs, const Segs& sg,
-                                                  float* __restrict__ logp, const int32_t* __restrict__ target,
-                                                  [[maybe_unused]] const GuideP& g = GuideP{nullptr, nullptr, 1.f},
-                                                  [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
+                                                     RunState* __restrict__ rs, Segs sg, int compact,
+                                                     [[maybe_unused]] float* __restrict__ logp, [[maybe_unused]] const int32_t* __restrict__ target,
+                                                     [[maybe_unused]] DrawGuideArg<GUIDED, TRUNC> ga) {
+    static_assert(GUIDED || !TRUNC, "a truncated session runs the guided form");
     __shared__ float lg[32];
     const int b = blockIdx.x;
     const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2744,18 +2672,21 @@ __device__ __forceinline__ void sample_block_body(const float* __restrict__ Hm, 
     if ((int)t < T[b]) {                                 // (T[b] <= Tmax: checked by the begin)
         const long bt = (long)b * Tmax + t;
         const int slot = order[bt];
-        const float* x = Hm + (long)sg.row(b, slot) * D;
-        if constexpr (GUIDED)
+        const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
+        if constexpr (GUIDED) {
+            GuideP g;
+            TruncP tr{0, 1.f, 0.f};
+            if constexpr (TRUNC) { g = ga.g; tr = ga.tr; } else g = ga;
             sample_row<SS_WAVES, MODE, true, TRUNC>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
                                                     MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
                                                     g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr);
-        else if constexpr (MODE == DRAW_SAMPLE)
+        } else if constexpr (MODE == DRAW_SAMPLE)
             sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
         else
             sample_row<SS_WAVES, MODE>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg, logp + bt,
                                        MODE == DRAW_SCORE ? target[bt] : 0);
     } else {
-        __syncthreads();                                 // (as sample_step_body: every wave has read the step before thread 0 goes on)
+        __syncthreads();                                 // (sample_row has one: every wave has read the step before thread 0 goes on)
     }
     if (threadIdx.x == 0) {
         __threadfence();
@@ -2764,38 +2695,6 @@ __device__ __forceinline__ void sample_block_body(const float* __restrict__ Hm, 
             __hip_atomic_store(&rs->step, step + gridDim.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-}
-__global__ void __launch_bounds__(64 * SS_WAVES) sample_block_k(const float* __restrict__ Hm, int D, HeadW w,
-                                                     int32_t* __restrict__ tokens,
-                                                     const int32_t* __restrict__ order,
-                                                     const int32_t* __restrict__ T, int Tmax,
-                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg) {
-    sample_block_body<DRAW_SAMPLE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, nullptr, nullptr);
-}
-template <int MODE>
-__global__ void __launch_bounds__(64 * SS_WAVES) sample_block_logp_k(const float* __restrict__ Hm, int D, HeadW w,
-                                                     int32_t* __restrict__ tokens,
-                                                     const int32_t* __restrict__ order,
-                                                     const int32_t* __restrict__ T, int Tmax,
-                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg,
-                                                     float* __restrict__ logp, const int32_t* __restrict__ target) {
-    static_assert(MODE == DRAW_RECORD || MODE == DRAW_SCORE, "the plain draw is sample_block_k");
-    sample_block_body<MODE>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target);
-}
-template <int MODE, bool TRUNC = false>
-__global__ void __launch_bounds__(64 * SS_WAVES) sample_block_guided_k(const float* __restrict__ Hm, int D, HeadW w,
-                                                     int32_t* __restrict__ tokens,
-                                                     const int32_t* __restrict__ order,
-                                                     const int32_t* __restrict__ T, int Tmax,
-                                                     const float* __restrict__ q_noise, int q_rows, int q_off,
-                                                     RunState* __restrict__ rs, Segs sg,
-                                                     float* __restrict__ logp, const int32_t* __restrict__ target, GuideArg<TRUNC> g) {
-    if constexpr (TRUNC)
-        sample_block_body<MODE, true, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g.g, g.tr);
-    else
-        sample_block_body<MODE, true>(Hm, D, w, tokens, order, T, Tmax, q_noise, q_rows, q_off, rs, sg, logp, target, g);
 }
 
 // ------------------------------------------------------------------------------------------------
