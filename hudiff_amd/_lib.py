@@ -36,6 +36,7 @@ EXPORTS = [
     "hd_set_guide", "hd_set_slots_per_step", "hd_set_slot_policy", "hd_sample_order",
     "hd_set_truncation",
     "hd_set_beam", "hd_beam_state",
+    "hd_set_budget", "hd_mutation_count",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -77,6 +78,11 @@ class HdGuide(C.Structure):
 class HdTruncation(C.Structure):
     """include/hudiff_hip.h "truncated sampling": the next begin on the handle consumes it."""
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float)]
+
+
+class HdBudget(C.Structure):
+    """include/hudiff_hip.h "mutation budget": hd_set_budget copies the arrays; the next begin on the handle consumes the budget."""
+    _fields_ = [("B", C.c_int32), ("origin", C.POINTER(C.c_int32)), ("max_mutations", C.POINTER(C.c_int32))]
 
 
 class HudiffError(RuntimeError):
@@ -144,6 +150,8 @@ def load():
     lib.hd_set_truncation.argtypes = [vp, P(HdTruncation)]
     lib.hd_set_beam.argtypes = [vp, C.c_int32]
     lib.hd_beam_state.argtypes = [vp, f32p, i32p, f32p]
+    lib.hd_set_budget.argtypes = [vp, P(HdBudget)]
+    lib.hd_mutation_count.argtypes = [vp, i32p]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

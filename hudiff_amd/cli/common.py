@@ -146,9 +146,46 @@ def add_beam_args(p):
     return p
 
 
+def max_mutations_arg(v):
+    n = int(v)
+    if n < 0:
+        import argparse
+        raise argparse.ArgumentTypeError(f"{v}: an integer >= 0")
+    return n
+
+
+def add_budget_args(p):
+    """--max_mutations of the four samplers (mutation budget, include/hudiff_hip.h); without it the run is today's."""
+    p.add_argument("--max_mutations", type=max_mutations_arg, default=None,
+                   help="mutation budget: every written sequence differs from its input in at most N of the sampled positions -- a row "
+                        "that has changed N of them keeps the input's residue from then on; composes with --beam (the W most likely "
+                        "humanizations with at most N mutations), the guide flags, --slot_policy confident and --temperature 0")
+    return p
+
+
+def apply_budget_args(args, jobs, logger=None):
+    """-> {"max_mutations": N} for sample_jobs[_with_retry] / beam_jobs, or {} without the flag (the calls are then exactly today's).
+    The origin a job's changes are counted from is its ``origin`` field: the input's own residue at every sampled slot."""
+    n = getattr(args, "max_mutations", None)
+    if n is None:
+        return {}
+    missing = [j.name for j in jobs if j.origin is None]
+    if missing:
+        raise ValueError(f"--max_mutations: input {missing[0]!r} carries no origin tokens")
+    if logger is not None:
+        logger.info("Mutation budget: at most {} of the sampled positions change".format(n))
+    return {"max_mutations": int(n)}
+
+
 def parse_with_beam(p, argv):
-    """parse_args, and the combinations --beam does not take are argparse errors."""
+    """parse_args, and the combinations --beam and --max_mutations do not take are argparse errors."""
     args = p.parse_args(argv)
+    if getattr(args, "max_mutations", None) is not None:
+        if int(args.slots_per_step) > 1:
+            p.error("--max_mutations counts one slot per forward: not together with --slots_per_step > 1")
+        if args.beam and not (args.top_k in (0, 22) and args.top_p >= 1.0 and args.min_p == 0.0):
+            p.error("--max_mutations with --beam takes no truncation (--top_k / --top_p / --min_p): the cut may remove the only "
+                    "residue the budget still allows")
     if args.beam:
         if int(args.slots_per_step) > 1:
             p.error("--beam searches one slot per forward: not together with --slots_per_step > 1")
@@ -169,7 +206,7 @@ def run_beam(model, jobs, args, kind, logger=None):
     if logger is not None:
         logger.info("Beam search: width {} (dropout off, no noise)".format(args.beam))
     res = beam_jobs(model, jobs, args.beam, device_batch=getattr(args, "device_batch", 256), temperature=temperature,
-                    **apply_truncation_args(args, logger))
+                    **apply_truncation_args(args, logger), **apply_budget_args(args, jobs, logger))
     if res is None:
         return None
     tokens, score, _, live = res

@@ -20,7 +20,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, beam_walk, noise_in_reference_order, sample_jobs_with_retry, seed_all
-from .common import (add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
+from .common import (add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
                      write_logp_csv)
 
 
@@ -57,6 +57,7 @@ def build_parser():
     add_guide_args(p)
     add_block_args(p)
     add_beam_args(p)
+    add_budget_args(p)
     return p
 
 
@@ -114,7 +115,8 @@ def main(argv=None):
         tok, reg, loc = I.nanobody_row(h_dict, inpaint_sample=args.inpaint_sample)
         if args.sample_order == "shuffle":
             np.random.shuffle(loc)                                            # nanosample.py:314-315
-        jobs.append(Job(tokens=tok, region=reg, loc=loc, name=str(idx), parent={"h": line.vhhseq}))
+        jobs.append(Job(tokens=tok, region=reg, loc=loc, name=str(idx), parent={"h": line.vhhseq},
+                        origin=np.array(I._TK.seq2idx(I.slot_residues(h_dict, "H")), np.int32)))
 
     # nanosample.py:316-353: accept / re-sweep loop (a sample must parse as a heavy domain; the last try is
     # written regardless), run for all sequences at once
@@ -147,6 +149,7 @@ def main(argv=None):
         if temperature != 1.0:
             more["temperature"] = temperature
         more.update(apply_block_args(args, jobs, logger))
+        more.update(apply_budget_args(args, jobs, logger))
         written = sample_jobs_with_retry(model, jobs, args.batch_size, args.seed, want=args.sample_number,
                                          tries=args.try_number, accept=accept,
                                          device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise, **more)

@@ -27,7 +27,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, noise_in_reference_order, sample_jobs, seed_all
-from .common import (add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
+from .common import (add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
                      write_logp_csv)
 
 
@@ -74,6 +74,7 @@ def build_parser():
     add_guide_args(p)
     add_block_args(p)
     add_beam_args(p)
+    add_budget_args(p)
     return p
 
 
@@ -193,7 +194,7 @@ def main(argv=None):
             if args.sample_order == "shuffle":
                 np.random.shuffle(loc)
             jobs.append(Job(tokens=tok, region=reg, loc=loc, chain=chain, name=str(line.name),
-                            parent={"h": line.h_seq, "l": line.l_seq, "tokens": parent}))
+                            parent={"h": line.h_seq, "l": line.l_seq, "tokens": parent}, origin=parent.astype(np.int32)))
             continue
         if numbered is None:
             h_dict, h_type = I.number_sequence(line.h_seq, args.numbering)
@@ -205,7 +206,7 @@ def main(argv=None):
         if args.sample_order == "shuffle":
             np.random.shuffle(loc)                                           # sample.py:497-498
         jobs.append(Job(tokens=tok, region=reg, loc=loc, chain=chain, name=str(line.name),
-                        parent={"h": line.h_seq, "l": line.l_seq, "tokens": parent}))
+                        parent={"h": line.h_seq, "l": line.l_seq, "tokens": parent}, origin=parent.astype(np.int32)))
 
     # sample.py:499-538: with similarity search one pass gives the single output row; without it the loop
     # re-sweeps until sample_number rows have been written (batch_size rows per pass)
@@ -233,6 +234,7 @@ def main(argv=None):
         if temperature != 1.0:
             more["temperature"] = temperature
         more.update(apply_block_args(args, jobs, logger))
+        more.update(apply_budget_args(args, jobs, logger))
         result = sample_jobs(model, jobs, args.batch_size, args.seed, passes=passes, device_batch=args.device_batch,
                              dropout=args.dropout, q_noise=q_noise, **more)
         if args.logp_fpath:

@@ -21,7 +21,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
+from .common import add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
 
 
 def build_parser():
@@ -45,6 +45,7 @@ def build_parser():
     add_guide_args(p)
     add_block_args(p)
     add_beam_args(p)
+    add_budget_args(p)
     return p
 
 
@@ -101,9 +102,10 @@ def main(argv=None):
     h_dict, _ = I.number_sequence(mouse_aa_h, args.numbering)
     l_dict, l_type = I.number_sequence(mouse_aa_l, args.numbering)
     tok, reg, chain, loc = I.antibody_row(h_dict, l_dict, l_type, finetune=bool(args.finetune), pad_region=0)
+    origin = np.array(I._TK.seq2idx(I.slot_residues(h_dict, "H") + I.slot_residues(l_dict, "L")), np.int32)      # the input's own residues
     if args.sample_order == "shuffle":
         np.random.shuffle(loc)
-    job = Job(tokens=tok, region=reg, loc=loc, chain=chain, name=pdb_name)
+    job = Job(tokens=tok, region=reg, loc=loc, chain=chain, name=pdb_name, origin=origin)
     passes = max(0, -(-args.sample_number // args.batch_size))                 # every replica looked at counts (:212)
     live = None
     if args.beam:                                                              # the W best rows stand where the replicas stand
@@ -115,7 +117,8 @@ def main(argv=None):
     else:
         temperature = apply_guide_args(args, "ab", [job], logger)
         result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout,
-                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
+                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger),
+                             **apply_budget_args(args, [job], logger))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

@@ -22,7 +22,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
+from .common import add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
 from .nanosample import chain_is_valid
 
 
@@ -48,6 +48,7 @@ def build_parser():
     add_guide_args(p)
     add_block_args(p)
     add_beam_args(p)
+    add_budget_args(p)
     return p
 
 
@@ -89,7 +90,8 @@ def main(argv=None):
     if args.sample_order == "shuffle":
         np.random.shuffle(loc)
     passes = max(1, -(-args.sample_number // args.batch_size))
-    job = Job(tokens=tok, region=reg, loc=loc, name=pdb_name)
+    origin = np.array(I._TK.seq2idx(I.slot_residues(h_dict, "H")), np.int32)                                      # the input's own residues
+    job = Job(tokens=tok, region=reg, loc=loc, name=pdb_name, origin=origin)
     live = None
     if args.beam:                                                              # the W best rows stand where the replicas stand
         beam = run_beam(model, [job], args, "nb", logger)
@@ -100,7 +102,8 @@ def main(argv=None):
     else:
         temperature = apply_guide_args(args, "nb", [job], logger)
         result = sample_jobs(model, [job], args.batch_size, args.seed, passes=passes, dropout=args.dropout,
-                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger))
+                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger),
+                             **apply_budget_args(args, [job], logger))
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

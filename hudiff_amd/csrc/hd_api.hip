@@ -109,6 +109,9 @@ struct Workspace {
     // beam search (hd_set_beam): cumulative score [B], parent [B, Tmax], and the candidate table / step log-probabilities [B, 22] of the
     // last position run.  Allocated by the first beam session of the lane and regrown like the [B, Tmax] family (a regrow drops the graphs).
     float *bscore = nullptr, *bcand = nullptr, *blp = nullptr; int32_t* bparent = nullptr; size_t beam_capB = 0, beam_capT = 0;
+    // mutation budget (hd_set_budget): origin tokens [B, L] (indexed by slot), the row's budget [B] and its count of mutations so far [B].
+    // Allocated by the first budgeted session of the lane, regrown like the beam's buffers.
+    int32_t *borigin = nullptr, *bmax = nullptr, *bn = nullptr; size_t bud_capB = 0;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -177,7 +180,8 @@ struct SessionOpts {
     bool trunc = false;                              // truncated sampling; a truncated session always draws with the guided kernels (guide != GUIDE_NONE)
     TruncP tr{0, 1.f, 0.f};                          // its normalised parameters (kernel arguments)
     int W = 0;                                       // beam width; 0 = a draw, > 0: beam_cand_k + beam_select_k in its place
-    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W); }
+    bool budget = false;                             // mutation budget; a budgeted session always draws with the guided kernels (guide != GUIDE_NONE)
+    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget); }
     bool operator==(const SessionOpts& o) const { return tied() == o.tied(); }
 };
 
@@ -193,7 +197,8 @@ struct StepKey {
     int kernels = 0;                                 // kernel_set(): split kernels in use, ln_sync level, lane count
     SessionOpts o;                                   // (normalised: temperature 1 when unguided, the neutral TruncP when not truncated)
     const uint32_t* gallow = nullptr; const float* gbias = nullptr;     // the guide buffers the launch really reads: when guided / biased
-    auto tied() const { return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias); }
+    const int32_t *borigin = nullptr, *bmax = nullptr, *bn = nullptr;   // the budget buffers, when the session has one
+    auto tied() const { return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias, borigin, bmax, bn); }
     bool operator==(const StepKey& k) const { return tied() == k.tied(); }
 };
 
@@ -278,12 +283,15 @@ struct HdModel {
     bool s_has_q = false;
     bool logp_ready = false;                         // the lanes' logp buffers hold a finished recording session (hd_sample_logp after the end)
     // Session options (include/hudiff_hip.h "guided sampling", "block decoding", "slot policy", "truncated sampling", "beam search"): the
-    // hd_set_* functions leave them in `pending`, hd_set_guide its validated copy of the guide beside it; the next begin takes both
+    // hd_set_* functions leave them in `pending`, hd_set_guide / hd_set_budget their copies of the arrays beside it; the next begin takes all
     // (whether it succeeds or fails) and, if it succeeds, the session keeps them in `s` -- the guide on the device -- through restarts
     // and guard repeats.  After the end `s` describes the last session (hd_sample_logp, hd_beam_state).
     struct Guide { int32_t B = 0; bool has_allow = false; std::vector<uint32_t> allow; std::vector<float> bias; };
+    struct Budget { int32_t B = 0; std::vector<int32_t> origin, max_mut; };       // hd_set_budget's copy: [B, L], [B]
     SessionOpts pending, s;
     Guide guide;
+    Budget budget;
+    bool count_ready = false;                        // the lanes' bn buffers hold an ended budgeted session's counts (hd_mutation_count after the end)
     std::vector<float> beam_score0;                  // score of every row at the begin: 0 for the first row of a group, -inf for the others
     bool order_ready = false;                        // the lanes' order buffers hold an ended session's order (hd_sample_order after the end)
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
@@ -713,6 +721,23 @@ extern "C" HdStatus hd_set_guide(HdModel* m, const HdGuide* g) {
     if (g->bias) k.bias.assign(g->bias, g->bias + n * 22);
     m->pending.guide = g->bias ? GUIDE_ALLOW_BIAS : GUIDE_ALLOW;
     m->pending.temp = tp;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "mutation budget": copies; the next begin takes the copy and checks the visited slots.
+extern "C" HdStatus hd_set_budget(HdModel* m, const HdBudget* b) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_budget: null model");
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_budget: a sampling session is open (the budget belongs to the NEXT begin)");
+    m->budget = HdModel::Budget();
+    m->pending.budget = false;
+    if (!b) return HD_OK;
+    if (b->B <= 0) return fail(HD_ERR_INVALID, "hd_set_budget: B = %d", b->B);
+    if (!b->origin || !b->max_mutations) return fail(HD_ERR_INVALID, "hd_set_budget: null %s", b->origin ? "max_mutations" : "origin");
+    HdModel::Budget& k = m->budget;
+    k.B = b->B;
+    k.origin.assign(b->origin, b->origin + (size_t)b->B * m->L);
+    k.max_mut.assign(b->max_mutations, b->max_mutations + b->B);
+    m->pending.budget = true;
     return HD_OK;
 }
 
@@ -1812,6 +1837,7 @@ extern "C" HdStatus hd_forward(HdModel* m, const int32_t* tokens, const int32_t*
     if (m->in_session) return fail(HD_ERR_STATE, "hd_forward: a sampling session is open (hd_sample_end it first)");
     m->logp_ready = false;                           // (lane 0's workspace may be regrown below)
     m->order_ready = false;
+    m->count_ready = false;
     if (B < 0) return fail(HD_ERR_INVALID, "hd_forward: B = %d", B);
     if (B == 0) return HD_OK;
     HIP_TRY(hipSetDevice(m->device));
@@ -1868,14 +1894,20 @@ static void static_switch(int v, F&& f) {
     }
 }
 
+// The budget of the open session as the launches take it: all null without one.
+static BudgetP budget_arg(const HdModel* m) {
+    const Workspace& ws = cur(m).ws;
+    return m->s.budget ? BudgetP{ws.borigin, ws.bmax, ws.bn} : BudgetP{nullptr, nullptr, nullptr};
+}
+
 // The guide argument of a launch at level LV: GuideP (the neutral one without a guide), GuideTP when the launch truncates.
 template <int LV>
 static auto guide_arg(const HdModel* m) {
     if constexpr (LV == LV_PLAIN) {
-        return GuideP{nullptr, nullptr, 1.f};
+        return GuideP{nullptr, nullptr, 1.f, BudgetP{nullptr, nullptr, nullptr}};
     } else {
         const Workspace& ws = cur(m).ws;
-        const GuideP g{ws.gallow, m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s.temp};
+        const GuideP g{ws.gallow, m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s.temp, budget_arg(m)};
         if constexpr (LV == LV_TRUNC) return GuideTP{g, m->s.tr};
         else return g;
     }
@@ -1943,7 +1975,7 @@ static HdStatus beam_step(HdModel* m, const Segs& sg, bool prune) {
     });
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(beam_select_k, dim3(sg.B / m->s.W), dim3(BEAM_THREADS), 0, ln.stream, ws.tokens, ws.order, ws.T, m->sTmax, m->L, m->s.W, ln.rs,
-                       ws.bscore, ws.bparent, ws.logp, ws.bcand, ws.blp);
+                       ws.bscore, ws.bparent, ws.logp, ws.bcand, ws.blp, budget_arg(m));
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -1972,7 +2004,8 @@ struct BeginIn {
 };
 
 // The options against each other and against the call.
-static HdStatus check_options(const HdModel* m, const BeginIn& in, const SessionOpts& o, const HdModel::Guide& guide) {
+static HdStatus check_options(const HdModel* m, const BeginIn& in, const SessionOpts& o, const HdModel::Guide& guide,
+                              const HdModel::Budget& budget) {
     const int B = in.B, K = o.K, W = o.W;
     const bool confident = o.policy == HD_SLOTS_CONFIDENT, guided = o.guide != GUIDE_NONE;
     if (W > 0) {                                     // beam search: one slot per forward in the given order, no noise, no dropout
@@ -1998,6 +2031,38 @@ static HdStatus check_options(const HdModel* m, const BeginIn& in, const Session
         if (guide.B != B) return fail(HD_ERR_INVALID, "hd_set_guide: the guide describes %d rows, the session has %d", guide.B, B);
         if (in.score && o.temp == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
+    }
+    if (o.budget) {
+        if (budget.B != B) return fail(HD_ERR_INVALID, "hd_set_budget: the budget describes %d rows, the session has %d", budget.B, B);
+        if (W > 0 && o.trunc)
+            return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a beam session with a mutation budget takes no truncation (the cut may remove the "
+                                            "only feasible token of an exhausted row)");
+        if (K > 1)
+            return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a mutation budget needs one slot per forward (slots per step %d: the draws of one "
+                                            "forward cannot see each other's count)", K);
+    }
+    return HD_OK;
+}
+
+// The budget against the visited slots (only those are looked at), the guide's allowed bits gathered by step, and the groups of a beam.
+static HdStatus check_budget(const HdModel* m, const BeginIn& in, const SessionOpts& o, const HdModel::Budget& budget,
+                             const std::vector<uint32_t>& gallow) {
+    const int B = in.B, Tmax = in.Tmax, W = o.W;
+    for (int b = 0; b < B; ++b) {
+        if (budget.max_mut[b] < 0) return fail(HD_ERR_INVALID, "hd_set_budget: max_mutations[%d] = %d is negative", b, budget.max_mut[b]);
+        const int a = W > 0 ? b / W * W : b;
+        if (budget.max_mut[b] != budget.max_mut[a])
+            return fail(HD_ERR_INVALID, "hd_set_budget: max_mutations[%d] = %d differs from row %d, the first of its beam group (%d)", b,
+                        budget.max_mut[b], a, budget.max_mut[a]);
+        for (int t = 0; t < in.T[b]; ++t) {
+            const int s = in.order[(size_t)b * Tmax + t], og = budget.origin[(size_t)b * m->L + s];
+            if (og < 0 || og > 22) return fail(HD_ERR_INVALID, "hd_set_budget: origin[%d,%d] = %d (step %d) out of [0,22]", b, s, og, t);
+            if (og <= 21 && !((gallow[(size_t)b * Tmax + t] >> og) & 1u))
+                return fail(HD_ERR_INVALID, "hd_set_budget: origin %d at row %d slot %d (step %d) is not allowed by the guide (an exhausted row "
+                                            "must be able to draw)", og, b, s, t);
+            if (og != budget.origin[(size_t)a * m->L + s])
+                return fail(HD_ERR_INVALID, "hd_set_budget: origin[%d,%d] = %d differs from row %d, the first of its beam group", b, s, og, a);
+        }
     }
     return HD_OK;
 }
@@ -2120,8 +2185,15 @@ static HdStatus bufs_beam(Workspace& ws, size_t nB, size_t nT, F&& f) {
     return HD_OK;
 }
 
+// A budgeted session: origin [B, L], budget and count [B].
+template <typename F>
+static HdStatus bufs_budget(Workspace& ws, size_t nB, size_t nBL, F&& f) {
+    HD_TRY(f(&ws.borigin, nBL)); HD_TRY(f(&ws.bmax, nB)); HD_TRY(f(&ws.bn, nB));
+    return HD_OK;
+}
+
 // Grows a group: its old buffers are released now, not at the next free_ws, and the lane's graphs go -- a captured step holds the old
-// addresses.  group(f) is one of the three above with its sizes bound.
+// addresses.  group(f) is one of the four above with its sizes bound.
 template <typename G>
 static HdStatus regrow(HdModel::Lane& ln, G&& group) {
     Workspace& ws = ln.ws;
@@ -2139,7 +2211,7 @@ static HdStatus regrow(HdModel::Lane& ln, G&& group) {
 
 // Buffers and uploads of the lane m->cl.
 static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, int dm, const std::vector<int32_t>& target,
-                           const std::vector<uint32_t>& gallow, const std::vector<float>& gbias) {
+                           const std::vector<uint32_t>& gallow, const std::vector<float>& gbias, const HdModel::Budget& budget) {
     HdModel::Lane& ln = cur(m);
     const int B = in.B, Tmax = in.Tmax, Bl = ln.B, off = ln.row_off;
     const bool guided = o.guide != GUIDE_NONE, biased = o.guide == GUIDE_ALLOW_BIAS;
@@ -2173,6 +2245,16 @@ static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, 
         HIP_TRY(hipMemcpyAsync(ws.bscore, m->beam_score0.data() + off, (size_t)Bl * sizeof(float), hipMemcpyHostToDevice, ln.stream));
         HIP_TRY(hipMemsetAsync(ws.bparent, 0, need * sizeof(int32_t), ln.stream));
         HIP_TRY(hipMemsetAsync(ws.bcand, 0, (size_t)Bl * 22 * sizeof(float), ln.stream));
+    }
+    if (o.budget) {                                      // the lane's rows of the budget (a beam's lanes are cut at group boundaries); n = 0
+        if ((size_t)Bl > ws.bud_capB) {
+            ws.bud_capB = 0;
+            HD_TRY(regrow(ln, [&](auto f) { return bufs_budget(ws, (size_t)Bl, (size_t)Bl * m->L, f); }));
+            ws.bud_capB = (size_t)Bl;
+        }
+        HIP_TRY(hipMemcpyAsync(ws.borigin, budget.origin.data() + (size_t)off * m->L, (size_t)Bl * m->L * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+        HIP_TRY(hipMemcpyAsync(ws.bmax, budget.max_mut.data() + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+        HIP_TRY(hipMemsetAsync(ws.bn, 0, (size_t)Bl * sizeof(int32_t), ln.stream));
     }
     if (guided && Tmax > 0) {
         HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, nT * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
@@ -2213,7 +2295,7 @@ static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, 
 }
 
 // `o` and `guide`: what take_pending took.  The session's options are worked out on the local copy and reach m->s only with success.
-static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel::Guide& guide) {
+static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel::Guide& guide, const HdModel::Budget& budget) {
     if (!m || !in.tokens || !in.region || !in.T || (in.Tmax > 0 && !in.order)) return fail(HD_ERR_INVALID, "hd_sample_begin: null argument");
     if (!m->finalized) return fail(HD_ERR_STATE, "hd_sample_begin: call hd_finalize first");
     if (m->in_session) return fail(HD_ERR_STATE, "hd_sample_begin: session already open");
@@ -2225,12 +2307,14 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     m->nlanes = 1; m->cl = 0;
     m->logp_ready = false;
     m->order_ready = false;
+    m->count_ready = false;
     o.mode = in.score ? DRAW_SCORE : ((in.flags & HD_RECORD_LOGP) || o.W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
     // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
     // bias, temperature 1), under which g_j == logit_j bit for bit
-    if (o.trunc && o.guide == GUIDE_NONE) { o.guide = GUIDE_ALLOW; o.temp = 1.f; guide = HdModel::Guide(); guide.B = B; }
-    HD_TRY(check_options(m, in, o, guide));
-    if (B == 0) {                                    // no row: nothing to guide or truncate
+    // and so does a budgeted one: the budget rides in the guide argument of the guided kernels
+    if ((o.trunc || o.budget) && o.guide == GUIDE_NONE) { o.guide = GUIDE_ALLOW; o.temp = 1.f; guide = HdModel::Guide(); guide.B = B; }
+    HD_TRY(check_options(m, in, o, guide, budget));
+    if (B == 0) {                                    // no row: nothing to guide or truncate (a budget describes at least one row: check_options)
         o.guide = GUIDE_NONE; o.temp = 1.f; o.trunc = false; o.tr = TruncP{0, 1.f, 0.f};
         m->s = o; m->in_session = true;
         return HD_OK;
@@ -2242,6 +2326,7 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     std::vector<uint32_t> gallow;
     std::vector<float> gbias;
     if (o.guide != GUIDE_NONE) HD_TRY(gather_guide(m, in, o, guide, target, gallow, gbias));
+    if (o.budget) HD_TRY(check_budget(m, in, o, budget, gallow));
     const int dm = drop_mode_of(m, in.flags);
     if (dm == DROP_INJECT && (!in.enc_masks || !in.conv_masks)) return fail(HD_ERR_INVALID, "hd_sample_begin: HD_DROPOUT_INJECT needs masks");
     split_lanes(m, in, o, dm);
@@ -2249,7 +2334,7 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
         m->beam_score0.assign((size_t)B, -INFINITY);
         for (int b = 0; b < B; b += o.W) m->beam_score0[b] = 0.f;
     }
-    for (m->cl = 0; m->cl < m->nlanes; ++m->cl) HD_TRY(lane_begin(m, in, o, dm, target, gallow, gbias));
+    for (m->cl = 0; m->cl < m->nlanes; ++m->cl) HD_TRY(lane_begin(m, in, o, dm, target, gallow, gbias, budget));
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
     m->cl = 0;
     m->s_row0 = in.row0;
@@ -2259,20 +2344,23 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
 }
 
 // What the hd_set_* functions left is taken by the begin that follows, whatever becomes of that begin (hd_forward neither uses nor clears it).
-static SessionOpts take_pending(HdModel* m, HdModel::Guide* guide) {
+static SessionOpts take_pending(HdModel* m, HdModel::Guide* guide, HdModel::Budget* budget) {
     if (!m) return SessionOpts();
     const SessionOpts o = m->pending;
     *guide = std::move(m->guide);
+    *budget = std::move(m->budget);
     m->pending = SessionOpts();
     m->guide = HdModel::Guide();
+    m->budget = HdModel::Budget();
     return o;
 }
 
 static HdStatus begin_session(HdModel* m, const BeginIn& in) {
     HdModel::Guide guide;
-    const SessionOpts o = take_pending(m, &guide);
+    HdModel::Budget budget;
+    const SessionOpts o = take_pending(m, &guide, &budget);
     const bool was_open = m && m->in_session;
-    const HdStatus s = sample_begin_impl(m, in, o, guide);
+    const HdStatus s = sample_begin_impl(m, in, o, guide, budget);
     if (s != HD_OK && m && !was_open) {          // a failure half-way through the lane loop must not leave lane state behind
         m->cl = 0; m->nlanes = 1; m->sB = 0; m->timed = false;
         m->s = SessionOpts();                    // (hd_sample_logp / hd_beam_state of an earlier session then answer as for a plain one)
@@ -2308,6 +2396,7 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (m->s.mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
+        if (m->s.budget) HIP_TRY(hipMemsetAsync(ln.ws.bn, 0, (size_t)ln.B * sizeof(int32_t), ln.stream));      // nothing spent yet
         if (m->s.W > 0) {                             // beam search: only the first row of every group is live again
             HIP_TRY(hipMemcpyAsync(ln.ws.bscore, m->beam_score0.data() + ln.row_off, (size_t)ln.B * sizeof(float), hipMemcpyHostToDevice, ln.stream));
             HIP_TRY(hipMemsetAsync(ln.ws.bparent, 0, (size_t)ln.B * (m->sTmax > 0 ? m->sTmax : 1) * sizeof(int32_t), ln.stream));
@@ -2338,6 +2427,7 @@ static StepKey step_key(const HdModel* m, const HdModel::Lane& ln) {
     if (!k.o.trunc) k.o.tr = TruncP{0, 1.f, 0.f};
     k.gallow = k.o.guide != GUIDE_NONE ? ln.ws.gallow : nullptr;
     k.gbias = k.o.guide == GUIDE_ALLOW_BIAS ? ln.ws.gbias : nullptr;
+    if (k.o.budget) { k.borigin = ln.ws.borigin; k.bmax = ln.ws.bmax; k.bn = ln.ws.bn; }
     return k;
 }
 
@@ -2473,7 +2563,7 @@ static HdStatus sample_end_impl(HdModel* m, int32_t* tokens, bool* numeric) {
 
 extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_end: no open session");
-    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s.mode != DRAW_SAMPLE; m->order_ready = true; return HD_OK; }
+    if (m->sB == 0) { m->in_session = false; m->logp_ready = m->s.mode != DRAW_SAMPLE; m->order_ready = true; m->count_ready = m->s.budget; return HD_OK; }
     if (!tokens) { m->in_session = false; return fail(HD_ERR_INVALID, "hd_sample_end: null tokens"); }
     bool numeric = false;
     const HdStatus s = sample_end_impl(m, tokens, &numeric);
@@ -2483,6 +2573,7 @@ extern "C" HdStatus hd_sample_end(HdModel* m, int32_t* tokens) {
     if (s != HD_OK) return s;
     m->logp_ready = m->s.mode != DRAW_SAMPLE;        // hd_sample_logp stays legal until the next begin / hd_forward
     m->order_ready = true;                           // and so does hd_sample_order
+    m->count_ready = m->s.budget;                    // and hd_mutation_count
     if (numeric)
         return fail(HD_ERR_NUMERIC, "hd_sample: non-finite logits (NaN / inf) at some denoiser step -- weights or inputs out of range; "
                                     "the reference's torch.multinomial raises at this point");
@@ -2602,6 +2693,20 @@ extern "C" HdStatus hd_beam_state(HdModel* m, float* score, int32_t* parent, flo
         if (cand) HIP_TRY(hipMemcpyAsync(cand + (size_t)ln.row_off * 22, ln.ws.bcand, (size_t)ln.B * 22 * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
     }
     return readback_done(m, "hd_beam_state", "values are");
+}
+
+// include/hudiff_hip.h "mutation budget": n of every row as it stands.
+extern "C" HdStatus hd_mutation_count(HdModel* m, int32_t* n) {
+    if (!m || (!m->in_session && !m->count_ready)) return fail(HD_ERR_STATE, "hd_mutation_count: no budgeted session (open, or ended and not yet replaced)");
+    if (!m->s.budget) return fail(HD_ERR_STATE, "hd_mutation_count: the session has no mutation budget (hd_set_budget)");
+    if (m->sB == 0) return HD_OK;
+    if (!n) return fail(HD_ERR_INVALID, "hd_mutation_count: null n");
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(n + ln.row_off, ln.ws.bn, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+    }
+    return readback_done(m, "hd_mutation_count", "counts are");
 }
 
 // include/hudiff_hip.h "slot policy": the order the session has taken so far (a given-order session: the order it was given).

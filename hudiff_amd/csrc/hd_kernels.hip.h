@@ -2488,10 +2488,29 @@ __device__ __forceinline__ void ln_row_regs(const float* __restrict__ x, int D, 
 // argmax_j (logit_j + bias_j) over the allowed j (lowest index wins), no noise read or generated, and the recorded log-probability is
 // the one under temperature 1.  With all bits set, no bias and temperature 1, g_j == logit_j bit for bit (x / 1.0f == x).
 // The unguided instantiations contain none of this.
+//
+// BUDGET (run time; hd_set_budget, include/hudiff_hip.h "mutation budget"): a nullable pointer inside the guide argument, so no further
+// instantiation.  A budgeted session always runs the GUIDED form.  Row b has spent n[b] mutations; at slot s with origin o = origin[b, s]
+// it is exhausted iff o <= 21 and n[b] >= max_mut[b], and the allowed set of an exhausted draw is {o} -- everything else is the guided
+// draw on that set.  One workgroup owns a row (K = 1: checked by the begin), so n[b] is a plain load and a plain store by one lane; the
+// launch boundary orders step t's store before step t + 1's load.
+struct BudgetP {
+    const int32_t* origin;   // [B, L] of the lane, indexed by SLOT; nullptr = the session has no budget
+    const int32_t* max_mut;  // [B]
+    int32_t* n;              // [B]: mutations so far
+};
+// the origin of (b, slot) and whether the row is exhausted there: {o, o} when exhausted, {o, -1} otherwise; {22, -1} without a budget
+struct BudgetAt { int o, force; };
+__device__ __forceinline__ BudgetAt budget_at(const BudgetP& bu, int b, int L, int slot) {
+    if (!bu.origin) return BudgetAt{22, -1};
+    const int o = bu.origin[(long)b * L + slot];
+    return BudgetAt{o, (o <= 21 && bu.n[b] >= bu.max_mut[b]) ? o : -1};
+}
 struct GuideP {
     const uint32_t* allow;   // [B, Tmax] of the lane, gathered by step on the host (as `target`): bit j allows token j
     const float* bias;       // [B, Tmax, 22] or nullptr
     float temperature;       // 0 = greedy
+    BudgetP bud;             // mutation budget; origin == nullptr: none
 };
 enum { DRAW_SAMPLE = 0, DRAW_RECORD = 1, DRAW_SCORE = 2 };
 
@@ -2533,7 +2552,7 @@ struct DrawDist { float g, mx, e, esum; bool allowed, kept, greedy; };
 template <int NW, bool GUIDED, bool TRUNC>
 __device__ __forceinline__ bool draw_dist(const float* x, int D, const HeadW& w, const RunState* __restrict__ rs, float* lg,
                                           const uint32_t* __restrict__ g_allow, const float* __restrict__ g_bias, float g_temp,
-                                          [[maybe_unused]] const TruncP& tr, DrawDist& d) {
+                                          [[maybe_unused]] const TruncP& tr, DrawDist& d, [[maybe_unused]] int force = -1) {
     static_assert(GUIDED || !TRUNC, "a truncated session runs the guided form");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the guide of this (row, step): asked for before the decoder's dot products, used behind them (wave 0, lane j = token j)
@@ -2542,6 +2561,7 @@ __device__ __forceinline__ bool draw_dist(const float* x, int D, const HeadW& w,
     if constexpr (GUIDED) {
         if (wave == 0) {
             allowed = lane < 22 && ((*g_allow >> lane) & 1u);
+            if (force >= 0) allowed = lane == force;     // mutation budget, rule 1: an exhausted row's allowed set is its origin alone
             if (g_bias && lane < 22) gb = g_bias[lane];
         }
     }
@@ -2592,10 +2612,11 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
                                            const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
                                            float* lg, float* __restrict__ logp_out = nullptr, int target = 0,
                                            const uint32_t* __restrict__ g_allow = nullptr, const float* __restrict__ g_bias = nullptr,
-                                           float g_temp = 1.f, [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f}) {
+                                           float g_temp = 1.f, [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f},
+                                           [[maybe_unused]] const BudgetAt ba = BudgetAt{22, -1}, [[maybe_unused]] int32_t* n_mut = nullptr) {
     const int lane = threadIdx.x & 63;
     DrawDist d;
-    if (!draw_dist<NW, GUIDED, TRUNC>(x, D, w, rs, lg, g_allow, g_bias, g_temp, tr, d)) return;
+    if (!draw_dist<NW, GUIDED, TRUNC>(x, D, w, rs, lg, g_allow, g_bias, g_temp, tr, d, ba.force)) return;
     const float mylogit = d.g, mx = d.mx, e = d.e, esum = d.esum;
     [[maybe_unused]] const bool allowed = d.allowed, kept = d.kept, greedy = d.greedy;
     if constexpr (MODE == DRAW_SCORE) {
@@ -2606,6 +2627,10 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
             tokens[(long)b * L + slot] = target;
             float lp = (zt - mx) - logf(esum);
             if constexpr (TRUNC) lp = kt ? lp : -INFINITY;   // a target the cut removed has probability 0 under this sampler
+            if constexpr (GUIDED) {
+                if (ba.force >= 0 && target != ba.force) lp = -INFINITY;      // so has a mutation the budget no longer pays for
+                if (n_mut && ba.o <= 21 && target != ba.o) *n_mut += 1;       // rule 3 counts targets
+            }
             *logp_out = lp;
         }
         return;
@@ -2634,7 +2659,13 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
         int b2 = __shfl_xor(best, o);
         if (r2 > ratio || (r2 == ratio && b2 < best)) { ratio = r2; best = b2; }
     }
+    if constexpr (GUIDED) {
+        if (ba.force >= 0) best = ba.force;              // an exhausted draw writes its origin, whatever its logit is
+    }
     if (lane == 0) tokens[(long)b * L + slot] = best;
+    if constexpr (GUIDED) {
+        if (lane == 0 && n_mut && ba.o <= 21 && best != ba.o) *n_mut += 1;    // rule 3, behind the token store
+    }
     if constexpr (MODE == DRAW_RECORD) {
         const float zb = __shfl(mylogit, best);          // (after the reduction every lane holds the winner)
         if (lane == 0) *logp_out = (zb - mx) - logf(esum);
@@ -2651,7 +2682,7 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
 // saves the one-thread launch per step that advance_step_k was.
 // logp / target: [B, Tmax] of the lane (row b at step t); read and written by the recording and the teacher-forced modes only.
 // Nine instantiations: three modes x {plain, guided, guided + truncation}.  The guide argument is GuideP when GUIDED, GuideTP (the three
-// cut parameters behind the guide) when TRUNC, and an empty struct otherwise.
+// cut parameters behind the guide) when TRUNC, and an empty struct otherwise.  A mutation budget rides in GuideP (BudgetP) and adds none.
 constexpr int SS_WAVES = 16;
 struct NoGuide {};
 template <bool GUIDED, bool TRUNC> using DrawGuideArg = std::conditional_t<GUIDED, GuideArg<TRUNC>, NoGuide>;
@@ -2679,7 +2710,8 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __re
             if constexpr (TRUNC) { g = ga.g; tr = ga.tr; } else g = ga;
             sample_row<SS_WAVES, MODE, true, TRUNC>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
                                                     MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
-                                                    g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr);
+                                                    g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr,
+                                                    budget_at(g.bud, b, sg.L, slot), g.bud.origin ? g.bud.n + b : nullptr);
         } else if constexpr (MODE == DRAW_SAMPLE)
             sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
         else
@@ -2753,6 +2785,10 @@ __global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __rest
         GuideP g;
         if constexpr (TRUNC) g = ga.g; else g = ga;
         allowed = lane < 22 && ((g.allow[bi] >> lane) & 1u);
+        // mutation budget: the key is formed on the allowed set of rule 1, with n as it stands at the start of the forward -- {o} for an
+        // exhausted row, whose key is then expf(0) = 1.0f exactly, the smallest there is
+        const int force = budget_at(g.bud, b, sg.L, order[bi]).force;
+        if (force >= 0) allowed = lane == force;
         if (allowed) {
             if (g.bias) z += g.bias[bi * 22 + lane];
             z = z / (g.temperature == 0.f ? 1.f : g.temperature);
@@ -2854,16 +2890,22 @@ __global__ void __launch_bounds__(64 * SS_WAVES) beam_cand_k(const float* __rest
     const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
     DrawDist d;
     bool wave0;
+    [[maybe_unused]] int force = -1;
     if constexpr (GUIDED) {
         GuideP g;
         TruncP tr{0, 1.f, 0.f};
         if constexpr (TRUNC) { g = ga.g; tr = ga.tr; } else g = ga;
+        // mutation budget: lp is formed under the guide alone and NOT renormalised; the budget only removes candidates
+        force = budget_at(g.bud, b, sg.L, slot).force;
         wave0 = draw_dist<SS_WAVES, true, TRUNC>(x, D, w, rs, lg, g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr, d);
     } else {
         wave0 = draw_dist<SS_WAVES, false, false>(x, D, w, rs, lg, nullptr, nullptr, 1.f, TruncP{0, 1.f, 0.f}, d);
     }
     if (!wave0 || lane >= 22) return;
-    const float v = (d.allowed && d.kept) ? (d.g - d.mx) - logf(d.esum) : -INFINITY;
+    float v = (d.allowed && d.kept) ? (d.g - d.mx) - logf(d.esum) : -INFINITY;
+    if constexpr (GUIDED) {
+        if (force >= 0 && lane != force) v = -INFINITY;
+    }
     lp[(long)b * 22 + lane] = v;
     cand[(long)b * 22 + lane] = score[b] + v;
 }
@@ -2875,15 +2917,16 @@ __global__ void __launch_bounds__(64 * SS_WAVES) beam_cand_k(const float* __rest
 // row r is its parent's row with tokens[slot] = j, score = cand, parent[b, t] = w, logp[b, t] = lp[w, j].  No atomics on floats: the
 // result is a function of the table alone.  The last workgroup moves rs->step on, as the draw does.
 constexpr int BEAM_MAX_W = 64, BEAM_THREADS = 256, BEAM_MAX_L = 304;
-constexpr int BEAM_LDS = BEAM_MAX_W * 22 * 4 + BEAM_MAX_W * BEAM_MAX_L + BEAM_MAX_W * 4;
+constexpr int BEAM_LDS = BEAM_MAX_W * 22 * 4 + BEAM_MAX_W * BEAM_MAX_L + BEAM_MAX_W * 4 + BEAM_MAX_W * 4;
 static_assert(lds_fill_ok(BEAM_LDS, BEAM_THREADS), "beam_select_k: LDS co-residency rule");
 __global__ void __launch_bounds__(BEAM_THREADS) beam_select_k(int32_t* __restrict__ tokens, const int32_t* __restrict__ order,
                                                     const int32_t* __restrict__ T, int Tmax, int L, int W, RunState* __restrict__ rs,
                                                     float* __restrict__ score, int32_t* __restrict__ parent, float* __restrict__ logp,
-                                                    const float* __restrict__ cand, const float* __restrict__ lp) {
+                                                    const float* __restrict__ cand, const float* __restrict__ lp, BudgetP bud) {
     __shared__ float key[BEAM_MAX_W * 22];
     __shared__ uint8_t stage[BEAM_MAX_W * BEAM_MAX_L];
     __shared__ int sel[BEAM_MAX_W];
+    __shared__ int nst[BEAM_MAX_W];                      // mutation budget: n of every row of the group, staged like the token rows
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * W;                       // first row of the group
     const uint32_t t = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2895,6 +2938,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) beam_select_k(int32_t* __restric
             key[i] = c > -INFINITY ? c : -INFINITY;      // (NaN compares false)
         }
         for (int i = tid; i < W * L; i += BEAM_THREADS) stage[i] = (uint8_t)tokens[(long)b0 * L + i];
+        if (bud.origin && tid < W) nst[tid] = bud.n[b0 + tid];
         __syncthreads();
         for (int i = tid; i < N; i += BEAM_THREADS) {
             const float c = key[i];
@@ -2915,6 +2959,10 @@ __global__ void __launch_bounds__(BEAM_THREADS) beam_select_k(int32_t* __restric
             score[b0 + tid] = cand[(long)b0 * 22 + s];
             parent[bt] = pw;
             logp[bt] = lp[(long)b0 * 22 + s];
+            if (bud.origin) {                            // the count travels with the row (the rows of a group share their origin: the begin)
+                const int o = bud.origin[(long)b0 * L + slot];
+                bud.n[b0 + tid] = nst[pw] + ((o <= 21 && s - pw * 22 != o) ? 1 : 0);
+            }
         }
     }
     __syncthreads();                                     // every wave has read the step before thread 0 goes on

@@ -14,6 +14,9 @@ the same definition in numpy float64 for host-side users; ``parse_constraints`` 
 
 A ``Truncation`` (top_k, top_p, min_p; include/hudiff_hip.h "truncated sampling") cuts the tail of that distribution in front of the
 draw; ``truncation_keep`` is its keep-set in float64, and ``guided_log_probs`` / ``confidence_keys`` take it as ``truncation=``.
+
+A ``Budget`` (origin, max_mutations; include/hudiff_hip.h "mutation budget") caps the slots in which a row may differ from its origin;
+``budget_walk`` is its rules 1 and 3 in numpy.
 """
 from __future__ import annotations
 
@@ -116,6 +119,77 @@ class Truncation:
 
     def __repr__(self):
         return f"Truncation(top_k={self.top_k}, top_p={self.top_p}, min_p={self.min_p})"
+
+
+FREE = N_DRAW                            # origin of a slot that has none: never forced, never counted
+
+
+class Budget:
+    """origin: int32 [L] or [B, L], token 0..21 = the residue a draw at that slot is compared with, 22 (``FREE``) = the slot has no
+    origin; max_mutations: an int or int32 [B], >= 0.  A row that has written max_mutations tokens different from their origin draws
+    its origin at every origin-bearing slot from then on.  The [L] / scalar forms describe every row of whatever batch consumes it."""
+
+    def __init__(self, origin, max_mutations):
+        self.origin = np.ascontiguousarray(np.asarray(origin), dtype=np.int32)
+        self.max_mutations = np.asarray(max_mutations).astype(np.int32)      # (0-d stays 0-d: the scalar form)
+        if self.origin.ndim not in (1, 2):
+            raise ValueError(f"origin must be [L] or [B, L], got {self.origin.shape}")
+        if self.max_mutations.ndim not in (0, 1):
+            raise ValueError(f"max_mutations must be an integer or [B], got {self.max_mutations.shape}")
+        if np.asarray(max_mutations).dtype.kind not in "iu" or (self.max_mutations < 0).any():
+            raise ValueError(f"max_mutations must be integers >= 0, got {max_mutations!r}")
+
+    def batch(self, B, L):
+        """-> (origin int32 [B, L], max_mutations int32 [B]), the [L] / scalar forms broadcast to B rows."""
+        if self.origin.shape not in ((L,), (B, L)):
+            raise ValueError(f"origin must be [{L}] or [{B}, {L}], got {self.origin.shape}")
+        if self.max_mutations.shape not in ((), (B,)):
+            raise ValueError(f"max_mutations must be an integer or [{B}], got {self.max_mutations.shape}")
+        return (np.ascontiguousarray(np.broadcast_to(self.origin, (B, L))),
+                np.ascontiguousarray(np.broadcast_to(self.max_mutations, (B,))))
+
+    def take(self, rows):
+        """The budget of the rows ``rows`` of the batch this one describes (beam search: a replica takes the budget of its group)."""
+        rows = np.asarray(rows)
+        return Budget(self.origin if self.origin.ndim == 1 else self.origin[rows],
+                      self.max_mutations if self.max_mutations.ndim == 0 else self.max_mutations[rows])
+
+    @staticmethod
+    def stack(budgets, L):
+        """Per-row budgets ([L] / scalar forms, or None) -> one [B, L] budget; a row without one is free everywhere."""
+        origin = np.full((len(budgets), L), FREE, np.int32)
+        max_mut = np.zeros(len(budgets), np.int32)
+        for r, b in enumerate(budgets):
+            if b is None:
+                continue
+            o, m = b.batch(1, L)
+            origin[r], max_mut[r] = o[0], m[0]
+        return Budget(origin, max_mut)
+
+
+def budget_walk(tokens_written, origin, order, T, max_mutations):
+    """Rules 1 and 3 of include/hudiff_hip.h "mutation budget" in numpy.  tokens_written int [B, Tmax]: the token row b wrote at order
+    position t (of a finished session without a repeated slot: ``tokens[b, order[b, t]]``); origin int [B, L]; order int [B, Tmax];
+    T int [B]; max_mutations int [B] (or an int).  Returns ``(exhausted, n)``: bool [B, Tmax], position t met the row with its budget
+    spent at an origin-bearing slot (entries at t >= T[b] are False); int32 [B], the mutations counted over the whole row -- targets of
+    a scoring session are counted too, so n may pass max_mutations."""
+    w, origin, order = np.asarray(tokens_written), np.asarray(origin), np.asarray(order)
+    if origin.ndim != 2 or order.ndim != 2 or order.shape[0] != origin.shape[0] or w.shape != order.shape:
+        raise ValueError(f"origin must be [B, L], order and tokens_written [B, Tmax]; got {origin.shape}, {order.shape}, {w.shape}")
+    B, Tmax = order.shape
+    T = np.asarray(T).reshape(-1)
+    M = np.broadcast_to(np.asarray(max_mutations), (B,))
+    if T.shape != (B,):
+        raise ValueError(f"T must be [{B}], got {T.shape}")
+    exhausted = np.zeros((B, Tmax), bool)
+    n = np.zeros(B, np.int32)
+    for b in range(B):
+        for t in range(int(T[b])):
+            o = int(origin[b, order[b, t]])
+            exhausted[b, t] = o <= 21 and n[b] >= M[b]
+            if o <= 21 and int(w[b, t]) != o:
+                n[b] += 1
+    return exhausted, n
 
 
 def truncation_keep(g22, truncation):

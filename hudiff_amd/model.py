@@ -308,9 +308,32 @@ class _Denoiser:
         L.check(self._lib.hd_sample_order(self._h, L.ptr(order, C.c_int32)))
         return order
 
-    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None):
+    def set_budget(self, budget, B=None):
+        """hd_set_budget: the mutation budget (hudiff_amd.guide.Budget; None clears) of the NEXT sample / sample_begin / score /
+        score_begin on this handle, which consumes it whether it succeeds or fails (include/hudiff_hip.h "mutation budget").  ``B``:
+        rows of that session (needed when the origin is given as [L]; default: the rows of a [B, L] origin)."""
+        if budget is None:
+            L.check(self._lib.hd_set_budget(self._h, None))
+            return
+        if B is None:
+            if budget.origin.ndim != 2:
+                raise ValueError("set_budget: a budget whose origin is [L] needs the number of rows B")
+            B = budget.origin.shape[0]
+        origin, max_mut = budget.batch(int(B), self.max_len)
+        b = L.HdBudget(int(B), L.ptr(origin, C.c_int32), L.ptr(max_mut, C.c_int32))
+        L.check(self._lib.hd_set_budget(self._h, C.byref(b)))
+
+    def mutation_count(self, B=None):
+        """hd_mutation_count: int32 [B], the mutations every row of the open budgeted session has spent so far, or of the last one."""
+        B = self._session_B if B is None else B
+        n = np.zeros(B, dtype=np.int32)
+        L.check(self._lib.hd_mutation_count(self._h, L.ptr(n, C.c_int32)))
+        return n
+
+    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None, budget=None):
         """What the next begin consumes: the block size (the library is told only when it is not 1), the slot policy (told only when
-        it is not "given"), the truncation (told only when it cuts something) and the guide."""
+        it is not "given"), the truncation (told only when it cuts something), the budget (told only when there is one) and the
+        guide."""
         policy = self._policy_id(slot_policy)
         block = int(slots_per_step) != 1
         trunc = truncation is not None and not truncation.neutral
@@ -321,6 +344,8 @@ class _Denoiser:
                 L.check(self._lib.hd_set_slot_policy(self._h, policy))
             if trunc:
                 self.set_truncation(truncation)
+            if budget is not None:
+                self.set_budget(budget, B)
             if guide is not None:
                 self.set_guide(guide, B)
         except Exception:
@@ -330,11 +355,13 @@ class _Denoiser:
                 self._lib.hd_set_slot_policy(self._h, L.HD_SLOTS_GIVEN)
             if trunc:
                 self._lib.hd_set_truncation(self._h, None)
+            if budget is not None:
+                self._lib.hd_set_budget(self._h, None)
             raise
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1,
-               slot_policy="given", truncation=None):
+               slot_policy="given", truncation=None, budget=None):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
@@ -351,13 +378,17 @@ class _Denoiser:
         distribution cut to the kept tokens and renormalised, and a recorded logp is the token's under that distribution.  None or a
         neutral one (nothing cut) makes no call into the library.
 
+        ``budget``: a hudiff_amd.guide.Budget (origin tokens, max_mutations) for this call only: a row that has changed max_mutations
+        of its origin-bearing slots draws its origin from then on (include/hudiff_hip.h "mutation budget"); ``mutation_count()``
+        afterwards returns what every row spent.  One slot per forward only.
+
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
         are the same with and without it."""
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
-        self._arm(guide, B, slots_per_step, slot_policy, truncation)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
@@ -397,14 +428,14 @@ class _Denoiser:
         return score, parent, cand
 
     def beam_begin(self, tokens, region, chain, order, T, width, *, guide=None, truncation=None, dropout="off", graph=True, prune=True,
-                   lanes=2, seed=0, row0=0):
+                   lanes=2, seed=0, row0=0, budget=None):
         """hd_set_beam + hd_sample_begin: a beam session of width W on rows that are ALREADY replicated -- tokens [G*W, L], every row
         of a group equal to its first.  sample_run / sample_restart / sync / sample_tokens / sample_logp / beam_state / sample_end
         work on it; it always records."""
         tok, reg, chn, order, T, B, Tmax, _, _, _, _ = self._sample_args(tokens, region, chain, order, T, None, None, None)
         self.set_beam(width)
         try:
-            self._arm(guide, B, 1, "given", truncation)
+            self._arm(guide, B, 1, "given", truncation, budget)
         except Exception:
             self._lib.hd_set_beam(self._h, 0)        # (no begin will follow to consume it)
             raise
@@ -413,7 +444,7 @@ class _Denoiser:
                                           self._flags(dropout, graph, prune, lanes), int(seed), int(row0), None, None, None))
         self._session_B, self._session_Tmax = B, Tmax
 
-    def beam_search(self, tokens, region, chain, order, T, width, *, guide=None, truncation=None, lanes=2, graph=True):
+    def beam_search(self, tokens, region, chain, order, T, width, *, guide=None, truncation=None, lanes=2, graph=True, budget=None):
         """The W most likely, pairwise different completions of every row along its visiting order, ranked: tokens [G, L], order
         [G, Tmax], T [G] as for ``sample``; ``width`` = W in [1, 64].  Each row is replicated W times, a [G, ...] guide is expanded to
         [G*W, ...], the session runs on the device (include/hudiff_hip.h "beam search": dropout off, no noise) and ``parent`` is
@@ -421,7 +452,9 @@ class _Denoiser:
             tokens [G, W, L]     the final rows of every group, best first
             score  [G, W]        their cumulative log-probability (-inf for a dead row: fewer than W sequences exist)
             logp   [G, W, Tmax]  the step values along each final row's own history, aligned to order positions
-            live   [G, W]        score is finite."""
+            live   [G, W]        score is finite.
+        ``budget``: a hudiff_amd.guide.Budget over the G groups: the W most likely completions with at most max_mutations changes from
+        the origin, ranked by their log-likelihood under the guide alone (the budget removes candidates, it does not rescale them)."""
         from .guide import beam_backtrack
         W = int(width)
         if isinstance(width, (bool, float)) or W != width or not 1 <= W <= L.BEAM_MAX_WIDTH:
@@ -448,7 +481,11 @@ class _Denoiser:
         if guide is not None:
             guide.batch(G, self.max_len)             # (shape check against the groups as given)
             guide = guide.take(rep)
-        self.beam_begin(tok[rep], reg[rep], chn, order[rep], T[rep], W, guide=guide, truncation=truncation, lanes=lanes, graph=graph)
+        if budget is not None:
+            budget.batch(G, self.max_len)            # (shape check against the groups as given)
+            budget = budget.take(rep)
+        self.beam_begin(tok[rep], reg[rep], chn, order[rep], T[rep], W, guide=guide, truncation=truncation, lanes=lanes, graph=graph,
+                        budget=budget)
         Tmax = order.shape[1]
         if G and Tmax:
             try:
@@ -462,9 +499,9 @@ class _Denoiser:
 
     # -- likelihood of given sequences -------------------------------------------------------------
     def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given",
-                   truncation=None):
+                   truncation=None, budget=None):
         logp = np.zeros((B, Tmax), dtype=np.float32)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
@@ -474,7 +511,7 @@ class _Denoiser:
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given",
-              truncation=None):
+              truncation=None, budget=None):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -497,9 +534,18 @@ class _Denoiser:
 
         ``slot_policy`` = "confident": teacher-forced under the confident sampler -- ``order[b, :T[b]]`` is the candidate list, the
         library picks the visiting order (``sample_order()`` afterwards) and logp[b, t] belongs to position t of THAT order.  The slot
-        of step t depends on the steps before it, so there is no step-parallel form: ``parallel=True`` raises, None runs the loop."""
+        of step t depends on the steps before it, so there is no step-parallel form: ``parallel=True`` raises, None runs the loop.
+
+        ``budget``: the values are log-probabilities under the budgeted sampler (hudiff_amd.guide.Budget): at a position where the row
+        has spent its budget the origin scores 0 and any other token -inf (no error).  Whether a position is exhausted depends on the
+        steps before it, so there is no step-parallel form either."""
         K = int(slots_per_step)
         confident = self._policy_id(slot_policy) != L.HD_SLOTS_GIVEN
+        if budget is not None:
+            if parallel:
+                raise ValueError("step-parallel scoring cannot follow a mutation budget: whether step t is exhausted depends on the "
+                                 "steps before it; use parallel=False (or None)")
+            parallel = False
         if confident and parallel:
             raise ValueError("step-parallel scoring cannot follow slot_policy='confident': the slot of step t depends on the steps "
                              "before it; use parallel=False (or None)")
@@ -512,7 +558,7 @@ class _Denoiser:
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
         flags = self._flags(dropout, graph, prune, lanes)
         if not parallel:
-            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy, truncation)
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy, truncation, budget)
         else:
             from . import scoring
             x = scoring.expand_steps(tok, reg, chn, order, T, slots_per_step=K)      # (K outside [1, 64]: ValueError)
@@ -539,11 +585,11 @@ class _Denoiser:
         return logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None):
+                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None, budget=None):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
         last_run_ms / sample_logp work on it as on a sampling session."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
@@ -552,10 +598,10 @@ class _Denoiser:
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                      enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1,
-                     slot_policy="given", truncation=None):
+                     slot_policy="given", truncation=None, budget=None):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),

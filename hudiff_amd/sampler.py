@@ -34,6 +34,13 @@ class Job:
     name: str = ""
     parent: dict = field(default_factory=dict)
     guide: Optional[object] = None       # hudiff_amd.guide.Guide of this sequence: allow [L] / bias [L, 22] (its temperature is not used)
+    origin: Optional[np.ndarray] = None  # [L] tokens a mutation budget (max_mutations=) counts changes from; 22 = the slot is free; None = all free
+
+
+def _stack_budget(jb, L, max_mutations):
+    """The jobs' origins under one ``max_mutations`` -> hudiff_amd.guide.Budget [len(jb), L]; a job without an origin is free everywhere."""
+    from .guide import Budget
+    return Budget.stack([None if j.origin is None else Budget(j.origin, int(max_mutations)) for j in jb], L)
 
 
 def _id_runs(gids: np.ndarray, max_rows: int):
@@ -51,7 +58,7 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
                 job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1,
-                slot_policy: str = "given", return_order: bool = False, truncation=None):
+                slot_policy: str = "given", return_order: bool = False, truncation=None, max_mutations: Optional[int] = None):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -73,6 +80,9 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
 
     ``truncation``: a hudiff_amd.guide.Truncation (top_k, top_p, min_p) for every draw of every row (model.sample); None or a neutral
     one passes nothing on and the calls into the library are exactly today's.
+
+    ``max_mutations``: a mutation budget (model.sample ``budget=``): every row may differ from its job's ``origin`` in at most that many
+    of the slots it samples, counted anew in every pass; None passes nothing on and the calls into the library are exactly today's.
 
     ``return_order``: also returns (last) int32 [len(jobs), passes, replicas, Tmax], the order each row took (model.sample_order;
     under "given" the order it was handed), gathered like the log-probabilities."""
@@ -114,6 +124,8 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
         if guided:
             from .guide import Guide
             more = dict(more, guide=Guide.stack([j.guide for j in jb], L, temperature))
+        if max_mutations is not None:
+            more = dict(more, budget=_stack_budget(jb, L, max_mutations))
         for p in range(passes):
             tok = model.sample(tok, reg, chain, order, T, seed=seed + 1000003 * p, row0=int(gids[cs]), dropout=dropout,
                                q_noise=None if q_noise is None else np.ascontiguousarray(q_noise[p][:Tmax, gids[cs:ce]]), **more)
@@ -140,14 +152,15 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
 
 
 def beam_jobs(model, jobs: Sequence[Job], width: int, *, device_batch: int = 256, all_ranks: bool = False, temperature: float = 1.0,
-              truncation=None):
+              truncation=None, max_mutations: Optional[int] = None):
     """Beam search (model.beam_search) of width W over every job: the W most likely, pairwise different completions of each along its
     ``loc``, ranked.  A launch takes floor(device_batch / W) jobs (at least one); jobs are sharded over ranks and gathered like tokens.
     Returns, on rank 0 (every rank when single-process or ``all_ranks``; None elsewhere),
         tokens int32 [len(jobs), W, L], score float32 [len(jobs), W], logp float32 [len(jobs), W, Tmax], live bool [len(jobs), W]
     as model.beam_search returns them.  ``temperature`` and the jobs' ``guide`` fields, and ``truncation``, shape the distribution the
     beam ranks under, as in ``sample_jobs``; temperature 0 has no distribution and is an error.  A job with replica states
-    (tokens [replicas, L]) is not a beam input."""
+    (tokens [replicas, L]) is not a beam input.  ``max_mutations``: as in ``sample_jobs`` -- the W most likely completions that differ
+    from the job's ``origin`` in at most that many sampled slots; it does not combine with a truncation."""
     W = int(width)
     if float(temperature) == 0.0:
         raise ValueError("beam search ranks under a distribution: temperature 0 (the greedy decode) has none")
@@ -177,6 +190,8 @@ def beam_jobs(model, jobs: Sequence[Job], width: int, *, device_batch: int = 256
             more["guide"] = Guide.stack([j.guide for j in jb], L, temperature)
         if truncation is not None and not truncation.neutral:
             more["truncation"] = truncation
+        if max_mutations is not None:
+            more["budget"] = _stack_budget(jb, L, max_mutations)
         e = s - lo + len(jb)
         tok[s - lo:e], score[s - lo:e], lp[s - lo:e], _ = model.beam_search(
             np.stack([j.tokens for j in jb]).astype(np.int32), np.stack([j.region for j in jb]).astype(np.int32), chain, order, T, W, **more)
@@ -234,7 +249,7 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
                            logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1,
-                           slot_policy: str = "given", truncation=None) -> List[List[np.ndarray]]:
+                           slot_policy: str = "given", truncation=None, max_mutations: Optional[int] = None) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -250,13 +265,16 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
 
     ``slot_policy``: as in ``sample_jobs`` (every sweep starts from the job's ``loc`` as the candidate list).
 
-    ``truncation``: as in ``sample_jobs``, for every sweep."""
+    ``truncation``: as in ``sample_jobs``, for every sweep.
+
+    ``max_mutations``: as in ``sample_jobs``; every sweep redraws every sampled slot and counts from 0, so every row written differs from
+    its job's ``origin`` in at most that many of them."""
     state = [{"left": want, "tries": tries, "tokens": None, "out": []} for _ in jobs]
     active = [j for j in range(len(jobs)) if want > 0 and tries > 0]
     sweep = 0
     while active:
         sub = [Job(tokens=jobs[j].tokens if state[j]["tokens"] is None else state[j]["tokens"], region=jobs[j].region,
-                   loc=jobs[j].loc, chain=jobs[j].chain, name=jobs[j].name, guide=jobs[j].guide) for j in active]
+                   loc=jobs[j].loc, chain=jobs[j].chain, name=jobs[j].name, guide=jobs[j].guide, origin=jobs[j].origin) for j in active]
         # noise is keyed by the ORIGINAL job index: a sequence's samples do not depend on which other inputs were
         # accepted earlier (or are in the file at all)
         # (q_noise: injected noise of sweep 0 only, [1, Tmax, len(jobs) * replicas, 22] keyed like the generated noise: parity runs)
@@ -269,6 +287,8 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
             more["slot_policy"] = slot_policy
         if truncation is not None and not truncation.neutral:
             more["truncation"] = truncation
+        if max_mutations is not None:
+            more["max_mutations"] = max_mutations
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:

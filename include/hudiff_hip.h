@@ -61,7 +61,8 @@ extern "C" {
                                  hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
                                  the struct HdGuide; block decoding added hd_set_slots_per_step; the slot policy added hd_set_slot_policy and
                                  hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation; beam search added hd_set_beam and
-                                 hd_beam_state */
+                                 hd_beam_state; the mutation budget added hd_set_budget, hd_mutation_count and the struct HdBudget -- entry points only, so the
+                                 version is unchanged */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -395,6 +396,58 @@ HdStatus hd_set_truncation(HdModel* m, const HdTruncation* t);   /* NULL clears 
  * most G of them.  hd_sample_run(t0, t1) takes any 0 <= t0 < t1 <= Tmax, as at K = 1. */
 HdStatus hd_set_beam(HdModel* m, int32_t width);   /* 0 clears */
 HdStatus hd_beam_state(HdModel* m, float* score /* [B] */, int32_t* parent /* [B, Tmax] */, float* cand /* [B, 22] */);
+
+/* ---- mutation budget ------------------------------------------------------------------------------
+ * A session may carry a budget: row b may differ from its ORIGIN in at most max_mutations[b] of the slots it visits.  This is the one
+ * option that depends on what the row has already drawn, so it has state: n[b], an int32 count of mutations so far, 0 at the begin and
+ * at hd_sample_restart (so the guards' repeats start from 0 as well).
+ *
+ * Order position t of row b, with s = order[b, t], o = origin[b, s], M = max_mutations[b]:
+ *   1. the row is EXHAUSTED at t iff o <= 21 and n[b] >= M.  The allowed set of the draw is then exactly {o}; otherwise it is the guide's
+ *      set (all 22 tokens without a guide);
+ *   2. everything else is the guided draw stage as it stands, on that allowed set and in the same arithmetic: g, mx, e, esum, the numeric
+ *      flag, the cut, the noise of position t, the argmax, logp.  An exhausted draw writes o and records logp = +0.0f exactly
+ *      (expf(0) = 1, logf(1) = 0); a greedy session (temperature 0) writes o;
+ *   3. after the token is written: if o <= 21 and token != o, n[b] += 1;
+ *   4. a free slot (o = 22) is never forced and never counted.
+ * All of it runs on the device inside the captured step; nothing is read back.  A budgeted session always runs the guided form of the
+ * draw, as a truncated one does (every bit set, no bias, temperature 1 when no guide is set), and a session whose rows never become
+ * exhausted produces, bit for bit, the tokens, logp, order and beam state of the same session without a budget.
+ *
+ * Scoring (hd_score_begin / hd_score) consumes a budget too: the target is written as always; an exhausted position whose target is
+ * not o records -inf, as a cut target does, and raises neither an error nor the numeric flag; rule 3 counts targets, so n may pass M.
+ * Scoring a budgeted session's tokens under the same origin, budget, order, guide and dropout key reproduces its logp bit for bit.
+ *
+ * Beam: n is part of the row state.  The candidate table is formed exactly as without a budget, then lp[b, j] = cand[b, j] = -inf where
+ * the row is exhausted and j != o.  lp[b, o] is NOT renormalised: the rows of one group have spent different amounts, and under a
+ * renormalised score an exhausted row would pay nothing for the rest of the sequence, so the search would reward spending the budget
+ * early.  The score of a beam row stays its log-likelihood under the guide alone; the budget is a feasibility constraint on candidates.
+ * The gather carries n with the row: n of rank r = n[parent] + (j != o and o <= 21), read before any row of the group is overwritten.
+ * o is always feasible, so a live row always has a finite candidate.
+ *
+ * Confident slot policy: the key of a remaining position is formed on the allowed set of rule 1, with n as it stands at the start of the
+ * forward.  Every origin-bearing slot of an exhausted row then has the key exactly 1.0f, the smallest possible, so those slots are
+ * taken first, in list order.
+ *
+ * Lifetime: as the guide -- hd_set_budget copies the arrays; one-shot: the NEXT hd_sample_begin / hd_sample / hd_score_begin / hd_score
+ * consumes it whether it succeeds or fails; hd_sample_restart and the guards' repeats keep it; hd_forward neither uses nor clears it.
+ * NULL clears a budget not yet consumed.  Inside an open session -> HD_ERR_STATE; a NULL handle, B <= 0 or a NULL array -> HD_ERR_INVALID.
+ *
+ * At the begin (only VISITED slots are checked or read, as for the guide): B differs -> HD_ERR_INVALID; a visited origin outside [0, 22]
+ * or a negative max_mutations[b] -> HD_ERR_INVALID; a visited slot whose o <= 21 is not allowed there by the guide -> HD_ERR_INVALID (an
+ * exhausted row must be able to draw); beam: a row whose max_mutations or visited origins differ from the first row of its group ->
+ * HD_ERR_INVALID; beam together with a truncation -> HD_ERR_UNSUPPORTED (the cut may remove the only feasible token); slots per step
+ * K > 1 -> HD_ERR_UNSUPPORTED (the K draws of one forward cannot see each other's count).
+ *
+ * hd_mutation_count copies n [B] out, rows in whole-batch order whatever the lane split.  Legal where hd_sample_logp is: inside a
+ * session, where it synchronises, and after it until the next begin.  A session without a budget -> HD_ERR_STATE. */
+typedef struct HdBudget {
+    int32_t B;                      /* rows described; must equal B of the session that consumes it */
+    const int32_t* origin;          /* [B, L]: token 0..21 = the residue a draw is compared with; 22 = the slot has no origin (free) */
+    const int32_t* max_mutations;   /* [B], >= 0 */
+} HdBudget;
+HdStatus hd_set_budget(HdModel* m, const HdBudget* b);      /* NULL clears */
+HdStatus hd_mutation_count(HdModel* m, int32_t* n /* [B] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
