@@ -37,6 +37,7 @@ EXPORTS = [
     "hd_set_truncation",
     "hd_set_beam", "hd_beam_state",
     "hd_set_budget", "hd_mutation_count",
+    "hd_set_confidence", "hd_sample_run_to_end", "hd_sample_progress", "hd_sample_forwards", "hd_sample_keys",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -152,6 +153,11 @@ def load():
     lib.hd_beam_state.argtypes = [vp, f32p, i32p, f32p]
     lib.hd_set_budget.argtypes = [vp, P(HdBudget)]
     lib.hd_mutation_count.argtypes = [vp, i32p]
+    lib.hd_set_confidence.argtypes = [vp, C.c_float]
+    lib.hd_sample_run_to_end.argtypes = [vp, C.c_int32, i32p]
+    lib.hd_sample_progress.argtypes = [vp, i32p]
+    lib.hd_sample_forwards.argtypes = [vp, i32p]
+    lib.hd_sample_keys.argtypes = [vp, f32p]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

@@ -107,18 +107,62 @@ def add_block_args(p):
                    help="which slots a forward fills: 'given' follows each row's visiting order; 'confident' lets the device pick, in "
                         "every forward, the --slots_per_step remaining slots whose distribution is most peaked (the order is then only "
                         "the list of slots to fill, and the tie-break)")
+    p.add_argument("--confidence", type=confidence_arg, default=None, metavar="TAU",
+                   help="confidence threshold in (0, 1], with --slot_policy confident: every forward fills, per row, all remaining "
+                        "slots whose top probability is at least TAU -- at least one, at most --slots_per_step -- so the number of "
+                        "forwards follows the model's certainty")
     return add_truncation_args(p)
 
 
-def apply_block_args(args, jobs, logger=None):
+def confidence_arg(v):
+    import argparse
+    try:
+        t = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{v}: a number in (0, 1]") from None
+    if not (t > 0.0 and t <= 1.0):                   # (NaN fails both)
+        raise argparse.ArgumentTypeError(f"{v}: a number in (0, 1]")
+    return t
+
+
+def check_confidence_args(p, args):
+    """The combinations --confidence does not take are argparse errors."""
+    if getattr(args, "confidence", None) is None:
+        return args
+    if args.slot_policy != "confident":
+        p.error("--confidence compares the confident policy's keys: it needs --slot_policy confident")
+    if getattr(args, "beam", 0):
+        p.error("--confidence is a sampling option: not together with --beam")
+    if getattr(args, "max_mutations", None) is not None:
+        p.error("--confidence may fill several slots per forward: not together with --max_mutations")
+    return args
+
+
+def log_forward_stats(stats, logger):
+    """What a --confidence run needed: mean and maximum forwards per row (this rank's rows)."""
+    if logger is not None and stats and stats.get("rows"):
+        logger.info("Forwards per row: mean {:.2f}, max {} ({} rows)".format(stats["forwards"] / stats["rows"], stats["max"], stats["rows"]))
+
+
+def apply_block_args(args, jobs, logger=None, forward_stats=None):
     """-> the keywords for sample_jobs[_with_retry] / score_jobs: {} at K = 1 in the given order (the calls are then exactly the
-    one-slot ones); with truncation flags, plus what apply_truncation_args returns."""
+    one-slot ones); with truncation flags, plus what apply_truncation_args returns.  ``forward_stats`` (samplers only): the dict a
+    --confidence run counts its forwards into (log_forward_stats)."""
     k = int(args.slots_per_step)
     more = apply_truncation_args(args, logger)
     if getattr(args, "slot_policy", "given") != "given":
         more["slot_policy"] = args.slot_policy
         if logger is not None:
             logger.info("Slot policy: {}".format(args.slot_policy))
+    if getattr(args, "confidence", None) is not None:
+        more["confidence"] = float(args.confidence)
+        if forward_stats is not None:
+            more["forward_stats"] = forward_stats
+        if logger is not None:
+            logger.info("Confidence threshold: {} (at most {} slots per forward)".format(args.confidence, k))
+        if k != 1:
+            more["slots_per_step"] = k
+        return more
     if k == 1:
         return more
     if logger is not None:
@@ -179,7 +223,7 @@ def apply_budget_args(args, jobs, logger=None):
 
 def parse_with_beam(p, argv):
     """parse_args, and the combinations --beam and --max_mutations do not take are argparse errors."""
-    args = p.parse_args(argv)
+    args = check_confidence_args(p, p.parse_args(argv))
     if getattr(args, "max_mutations", None) is not None:
         if int(args.slots_per_step) > 1:
             p.error("--max_mutations counts one slot per forward: not together with --slots_per_step > 1")

@@ -20,7 +20,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, beam_walk, noise_in_reference_order, sample_jobs_with_retry, seed_all
-from .common import (add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
+from .common import (add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, log_forward_stats, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_wrapped,
                      write_logp_csv)
 
 
@@ -148,11 +148,13 @@ def main(argv=None):
         temperature = apply_guide_args(args, "nb", jobs, logger)
         if temperature != 1.0:
             more["temperature"] = temperature
-        more.update(apply_block_args(args, jobs, logger))
+        forward_stats = {}
+        more.update(apply_block_args(args, jobs, logger, forward_stats))
         more.update(apply_budget_args(args, jobs, logger))
         written = sample_jobs_with_retry(model, jobs, args.batch_size, args.seed, want=args.sample_number,
                                          tries=args.try_number, accept=accept,
                                          device_batch=args.device_batch, dropout=args.dropout, log=rejected, q_noise=q_noise, **more)
+        log_forward_stats(forward_stats, logger)
     if rank != 0:
         return None
     if records is not None:

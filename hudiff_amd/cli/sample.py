@@ -27,7 +27,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, noise_in_reference_order, sample_jobs, seed_all
-from .common import (add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
+from .common import (add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, log_forward_stats, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, load_numbered, split_fasta_for_save, write_fasta_2line,
                      write_logp_csv)
 
 
@@ -233,10 +233,12 @@ def main(argv=None):
         temperature = apply_guide_args(args, "ab", jobs, logger)
         if temperature != 1.0:
             more["temperature"] = temperature
-        more.update(apply_block_args(args, jobs, logger))
+        forward_stats = {}
+        more.update(apply_block_args(args, jobs, logger, forward_stats))
         more.update(apply_budget_args(args, jobs, logger))
         result = sample_jobs(model, jobs, args.batch_size, args.seed, passes=passes, device_batch=args.device_batch,
                              dropout=args.dropout, q_noise=q_noise, **more)
+        log_forward_stats(forward_stats, logger)
         if args.logp_fpath:
             result, result_logp = result
     if rank != 0:

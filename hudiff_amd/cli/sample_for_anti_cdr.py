@@ -21,7 +21,7 @@ from .. import inputs as I
 from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint
 from ..model import model_selected
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
+from .common import add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, log_forward_stats, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta
 
 
 def build_parser():
@@ -116,9 +116,11 @@ def main(argv=None):
         result, live = beam[0][:, None], beam[2]
     else:
         temperature = apply_guide_args(args, "ab", [job], logger)
+        forward_stats = {}
         result = sample_jobs(model, [job], args.batch_size, args.seed, passes=max(passes, 1), dropout=args.dropout,
-                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger),
+                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger, forward_stats),
                              **apply_budget_args(args, [job], logger))
+        log_forward_stats(forward_stats, logger)
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

@@ -22,7 +22,7 @@ from .. import inputs as I
 from ..checkpoint import load_checkpoint, nanobody_model_from_checkpoint
 from ..model import NanoAntiTFNet
 from ..sampler import Job, sample_jobs, seed_all
-from .common import add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
+from .common import add_budget_args, apply_budget_args, add_beam_args, add_block_args, add_guide_args, parse_with_beam, run_beam, add_runtime_args, apply_block_args, log_forward_stats, apply_guide_args, relaunch_if_asked, get_logger, get_new_log_dir, read_fasta, split_fasta_for_save, write_fasta_wrapped
 from .nanosample import chain_is_valid
 
 
@@ -101,9 +101,11 @@ def main(argv=None):
         result, live = beam[0][:, None], beam[2]
     else:
         temperature = apply_guide_args(args, "nb", [job], logger)
+        forward_stats = {}
         result = sample_jobs(model, [job], args.batch_size, args.seed, passes=passes, dropout=args.dropout,
-                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger),
+                             **({} if temperature == 1.0 else {"temperature": temperature}), **apply_block_args(args, [job], logger, forward_stats),
                              **apply_budget_args(args, [job], logger))
+        log_forward_stats(forward_stats, logger)
     if rank != 0:
         return None
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")

@@ -27,7 +27,7 @@ from ..checkpoint import antibody_model_from_checkpoint, load_checkpoint, nanobo
 from ..model import NanoAntiTFNet, model_selected
 from ..sampler import Job
 from ..scoring import score_jobs
-from .common import add_block_args, add_runtime_args, apply_block_args, load_numbered, relaunch_if_asked
+from .common import add_block_args, add_runtime_args, apply_block_args, check_confidence_args, load_numbered, relaunch_if_asked
 
 MASKS = {"ab": ("finetune", "pretrain"), "nb": ("plain", "inpaint")}
 
@@ -109,7 +109,7 @@ def write_scores(path, jobs, res):
 
 def main(argv=None):
     parser = build_parser()
-    args = parser.parse_args(argv)
+    args = check_confidence_args(parser, parser.parse_args(argv))
     if args.slot_policy == "confident" and args.orders > 1:
         parser.error("--slot_policy confident takes --orders 1: the visiting order is the model's own (only ties ever see the list)")
     rc = relaunch_if_asked(args, "hudiff_amd.cli.score", argv)

@@ -112,6 +112,10 @@ struct Workspace {
     // mutation budget (hd_set_budget): origin tokens [B, L] (indexed by slot), the row's budget [B] and its count of mutations so far [B].
     // Allocated by the first budgeted session of the lane, regrown like the beam's buffers.
     int32_t *borigin = nullptr, *bmax = nullptr, *bn = nullptr; size_t bud_capB = 0;
+    // confidence threshold (hd_set_confidence): per row where its last forward started [B] and how many positions it took [B] (progress =
+    // their sum; slot_select_k writes both), and the forward number that drew each position [B, Tmax].  Allocated by the first threshold
+    // session of the lane, regrown like the beam's buffers.
+    int32_t *tfilled = nullptr, *tcnt = nullptr, *tfwd = nullptr; size_t th_capB = 0, th_capT = 0;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -181,7 +185,8 @@ struct SessionOpts {
     TruncP tr{0, 1.f, 0.f};                          // its normalised parameters (kernel arguments)
     int W = 0;                                       // beam width; 0 = a draw, > 0: beam_cand_k + beam_select_k in its place
     bool budget = false;                             // mutation budget; a budgeted session always draws with the guided kernels (guide != GUIDE_NONE)
-    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget); }
+    float cmax = 0.f;                                // confidence threshold: 1 / tau (a kernel argument), 0 = none; such a session is confident and guided
+    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget, cmax); }
     bool operator==(const SessionOpts& o) const { return tied() == o.tied(); }
 };
 
@@ -198,7 +203,10 @@ struct StepKey {
     SessionOpts o;                                   // (normalised: temperature 1 when unguided, the neutral TruncP when not truncated)
     const uint32_t* gallow = nullptr; const float* gbias = nullptr;     // the guide buffers the launch really reads: when guided / biased
     const int32_t *borigin = nullptr, *bmax = nullptr, *bn = nullptr;   // the budget buffers, when the session has one
-    auto tied() const { return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias, borigin, bmax, bn); }
+    const int32_t *tfilled = nullptr, *tcnt = nullptr, *tfwd = nullptr; // the threshold buffers, when the session has one
+    auto tied() const {
+        return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias, borigin, bmax, bn, tfilled, tcnt, tfwd);
+    }
     bool operator==(const StepKey& k) const { return tied() == k.tied(); }
 };
 
@@ -278,7 +286,11 @@ struct HdModel {
     int sB = 0, sTmax = 0;
     uint64_t s_row0 = 0;
     uint64_t s_seed = 0;                             // seed of the last hd_sample_begin / hd_sample_restart (range-guard re-run)
-    int s_steps = 0;                                 // steps enqueued since then (largest t1 of hd_sample_run)
+    int s_steps = 0;                                 // steps enqueued since then (largest t1 of hd_sample_run; a threshold session: forwards)
+    // threshold session: T of every row as the begin got it (hd_sample_run_to_end compares the progress with it), and whether the steps
+    // since the last begin / restart were run to the end, and in which chunks -- a guard's repeat then runs to the end again
+    std::vector<int32_t> sT;
+    bool ran_to_end = false; int end_chunk = 0;
     uint32_t sflags = 0;
     bool s_has_q = false;
     bool logp_ready = false;                         // the lanes' logp buffers hold a finished recording session (hd_sample_logp after the end)
@@ -658,6 +670,15 @@ extern "C" HdStatus hd_set_slots_per_step(HdModel* m, int32_t k) {
     if (k < 1 || k > 64) return fail(HD_ERR_INVALID, "hd_set_slots_per_step: k = %d outside [1, 64]", k);
     if (m->in_session) return fail(HD_ERR_STATE, "hd_set_slots_per_step: a sampling session is open (the block size belongs to the NEXT begin)");
     m->pending.K = k;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "confidence threshold": the next begin takes it; 0 clears.  The kernels get cmax = 1 / tau.
+extern "C" HdStatus hd_set_confidence(HdModel* m, float tau) {
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_confidence: null model");
+    if (!(tau >= 0.f && tau <= 1.f)) return fail(HD_ERR_INVALID, "hd_set_confidence: tau = %g outside [0, 1]", (double)tau);      // (NaN fails every comparison)
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_confidence: a sampling session is open (the threshold belongs to the NEXT begin)");
+    m->pending.cmax = tau == 0.f ? 0.f : 1.0f / tau;
     return HD_OK;
 }
 
@@ -1900,20 +1921,27 @@ static BudgetP budget_arg(const HdModel* m) {
     return m->s.budget ? BudgetP{ws.borigin, ws.bmax, ws.bn} : BudgetP{nullptr, nullptr, nullptr};
 }
 
+// The threshold of the open session as the launches take it: all null without one.
+static ThreshP thresh_arg(const HdModel* m) {
+    const Workspace& ws = cur(m).ws;
+    return m->s.cmax > 0.f ? ThreshP{ws.tfilled, ws.tcnt, ws.tfwd, m->s.cmax} : ThreshP{nullptr, nullptr, nullptr, 0.f};
+}
+
 // The guide argument of a launch at level LV: GuideP (the neutral one without a guide), GuideTP when the launch truncates.
 template <int LV>
 static auto guide_arg(const HdModel* m) {
     if constexpr (LV == LV_PLAIN) {
-        return GuideP{nullptr, nullptr, 1.f, BudgetP{nullptr, nullptr, nullptr}};
+        return GuideP{nullptr, nullptr, 1.f, BudgetP{nullptr, nullptr, nullptr}, ThreshP{nullptr, nullptr, nullptr, 0.f}};
     } else {
         const Workspace& ws = cur(m).ws;
-        const GuideP g{ws.gallow, m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s.temp, budget_arg(m)};
+        const GuideP g{ws.gallow, m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, m->s.temp, budget_arg(m), thresh_arg(m)};
         if constexpr (LV == LV_TRUNC) return GuideTP{g, m->s.tr};
         else return g;
     }
 }
 
-// The draw, sample_step_k: one workgroup per (row, order position of this forward), grid (B, K), whose last one advances the step by K.
+// The draw, sample_step_k: one workgroup per (row, order position of this forward), grid (B, K), whose last one advances the step by K
+// (a threshold session: by 1, and row b's workgroups beyond its count of this forward do nothing).
 // prune: the compact rows of a pruned tail (K == 1 only: one_step); otherwise the full hidden buffer.  The injected Exp(1) noise lives
 // once, for the whole batch, in the model (m->qnoise).
 static HdStatus draw(HdModel* m, const Segs& sg, bool prune) {
@@ -1957,7 +1985,7 @@ static HdStatus slot_choose(HdModel* m, const Segs& sg) {
     const bool guided = m->s.guide != GUIDE_NONE;
     hipLaunchKernelGGL(guided ? slot_select_k<true> : slot_select_k<false>, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order,
                        m->s.mode == DRAW_SCORE ? ws.target : nullptr, ws.T, m->sTmax, m->s.K, ln.rs, ws.conf, guided ? ws.gallow : nullptr,
-                       m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr);
+                       m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, thresh_arg(m));
     HIP_TRY(hipGetLastError());
     return HD_OK;
 }
@@ -2031,6 +2059,14 @@ static HdStatus check_options(const HdModel* m, const BeginIn& in, const Session
         if (guide.B != B) return fail(HD_ERR_INVALID, "hd_set_guide: the guide describes %d rows, the session has %d", guide.B, B);
         if (in.score && o.temp == 0.f)
             return fail(HD_ERR_INVALID, "hd_score_begin: a guide with temperature 0 (greedy decode) has no distribution to score under");
+    }
+    if (o.cmax > 0.f) {                              // confidence threshold: the count of a forward comes from the confident policy's keys
+        if (!confident)
+            return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a confidence threshold (hd_set_confidence) needs the confident slot policy "
+                                            "(hd_set_slot_policy): the given order has no keys to compare with it");
+        if (o.budget)
+            return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: a confidence threshold takes no mutation budget (the draws of one forward cannot "
+                                            "see each other's count, and a forward may take several)");
     }
     if (o.budget) {
         if (budget.B != B) return fail(HD_ERR_INVALID, "hd_set_budget: the budget describes %d rows, the session has %d", budget.B, B);
@@ -2192,8 +2228,23 @@ static HdStatus bufs_budget(Workspace& ws, size_t nB, size_t nBL, F&& f) {
     return HD_OK;
 }
 
+// A threshold session: start and count of the last forward [B], forward numbers [B, Tmax].
+template <typename F>
+static HdStatus bufs_thresh(Workspace& ws, size_t nB, size_t nT, F&& f) {
+    HD_TRY(f(&ws.tfilled, nB)); HD_TRY(f(&ws.tcnt, nB)); HD_TRY(f(&ws.tfwd, nT));
+    return HD_OK;
+}
+// Its state at the begin and at a restart: nothing filled, no forward run (fwd = -1 everywhere).
+static HdStatus thresh_reset(HdModel::Lane& ln, int Tmax) {
+    Workspace& ws = ln.ws;
+    HIP_TRY(hipMemsetAsync(ws.tfilled, 0, (size_t)ln.B * sizeof(int32_t), ln.stream));
+    HIP_TRY(hipMemsetAsync(ws.tcnt, 0, (size_t)ln.B * sizeof(int32_t), ln.stream));
+    HIP_TRY(hipMemsetAsync(ws.tfwd, 0xFF, (size_t)ln.B * (Tmax > 0 ? Tmax : 1) * sizeof(int32_t), ln.stream));
+    return HD_OK;
+}
+
 // Grows a group: its old buffers are released now, not at the next free_ws, and the lane's graphs go -- a captured step holds the old
-// addresses.  group(f) is one of the four above with its sizes bound.
+// addresses.  group(f) is one of the five above with its sizes bound.
 template <typename G>
 static HdStatus regrow(HdModel::Lane& ln, G&& group) {
     Workspace& ws = ln.ws;
@@ -2256,6 +2307,14 @@ static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, 
         HIP_TRY(hipMemcpyAsync(ws.bmax, budget.max_mut.data() + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
         HIP_TRY(hipMemsetAsync(ws.bn, 0, (size_t)Bl * sizeof(int32_t), ln.stream));
     }
+    if (o.cmax > 0.f) {                                  // the lane's rows start with nothing filled
+        if ((size_t)Bl > ws.th_capB || need > ws.th_capT) {
+            ws.th_capB = 0; ws.th_capT = 0;
+            HD_TRY(regrow(ln, [&](auto f) { return bufs_thresh(ws, (size_t)Bl, need, f); }));
+            ws.th_capB = (size_t)Bl; ws.th_capT = need;
+        }
+        HD_TRY(thresh_reset(ln, Tmax));
+    }
     if (guided && Tmax > 0) {
         HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, nT * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
         if (biased) HIP_TRY(hipMemcpyAsync(ws.gbias, gbias.data() + (size_t)off * Tmax * 22, nT * 22 * sizeof(float), hipMemcpyHostToDevice, ln.stream));
@@ -2267,6 +2326,7 @@ static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, 
         if (in.score) HIP_TRY(hipMemcpyAsync(ws.target, target.data() + (size_t)off * Tmax, nT * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
     }
     if (o.policy == HD_SLOTS_CONFIDENT && Tmax > 0) {    // what slot_select_k permutes, as uploaded: hd_sample_restart starts from the caller's list again
+        HIP_TRY(hipMemsetAsync(ws.conf, 0, nT * sizeof(float), ln.stream));        // (hd_sample_keys before the first forward reads zeros)
         HIP_TRY(hipMemcpyAsync(ws.order0, ws.order, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (in.score) HIP_TRY(hipMemcpyAsync(ws.target0, ws.target, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (guided) HIP_TRY(hipMemcpyAsync(ws.gallow0, ws.gallow, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
@@ -2304,6 +2364,7 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     HIP_TRY(hipSetDevice(m->device));
     m->sB = B; m->sTmax = Tmax; m->sflags = in.flags; m->s_has_q = in.q_noise != nullptr; m->timed = false; m->last_steps = 0;
     m->s_seed = in.seed; m->s_steps = 0; m->s_dirty = false;
+    m->ran_to_end = false; m->end_chunk = 0;
     m->nlanes = 1; m->cl = 0;
     m->logp_ready = false;
     m->order_ready = false;
@@ -2312,7 +2373,8 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
     // bias, temperature 1), under which g_j == logit_j bit for bit
     // and so does a budgeted one: the budget rides in the guide argument of the guided kernels
-    if ((o.trunc || o.budget) && o.guide == GUIDE_NONE) { o.guide = GUIDE_ALLOW; o.temp = 1.f; guide = HdModel::Guide(); guide.B = B; }
+    // and a threshold session: its progress rides there too
+    if ((o.trunc || o.budget || o.cmax > 0.f) && o.guide == GUIDE_NONE) { o.guide = GUIDE_ALLOW; o.temp = 1.f; guide = HdModel::Guide(); guide.B = B; }
     HD_TRY(check_options(m, in, o, guide, budget));
     if (B == 0) {                                    // no row: nothing to guide or truncate (a budget describes at least one row: check_options)
         o.guide = GUIDE_NONE; o.temp = 1.f; o.trunc = false; o.tr = TruncP{0, 1.f, 0.f};
@@ -2338,6 +2400,7 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     for (int l = 0; l < m->nlanes; ++l) HIP_TRY(hipStreamSynchronize(m->lane[l].stream));
     m->cl = 0;
     m->s_row0 = in.row0;
+    m->sT.assign(in.T, in.T + B);
     m->s = o;
     m->in_session = true;
     return HD_OK;
@@ -2385,6 +2448,7 @@ extern "C" HdStatus hd_score_begin(HdModel* m, const int32_t* tokens, const int3
 
 extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_restart: no open session");
+    m->ran_to_end = false;
     if (m->sB == 0) { m->s_seed = seed; m->s_steps = 0; return HD_OK; }
     HIP_TRY(hipSetDevice(m->device));
     // a guard that fired in the sample being discarded still switches its kernels off (and is counted) before the flags are cleared:
@@ -2397,6 +2461,7 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (m->s.mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
         if (m->s.budget) HIP_TRY(hipMemsetAsync(ln.ws.bn, 0, (size_t)ln.B * sizeof(int32_t), ln.stream));      // nothing spent yet
+        if (m->s.cmax > 0.f) HD_TRY(thresh_reset(ln, m->sTmax));                                                // nothing filled yet
         if (m->s.W > 0) {                             // beam search: only the first row of every group is live again
             HIP_TRY(hipMemcpyAsync(ln.ws.bscore, m->beam_score0.data() + ln.row_off, (size_t)ln.B * sizeof(float), hipMemcpyHostToDevice, ln.stream));
             HIP_TRY(hipMemsetAsync(ln.ws.bparent, 0, (size_t)ln.B * (m->sTmax > 0 ? m->sTmax : 1) * sizeof(int32_t), ln.stream));
@@ -2428,13 +2493,15 @@ static StepKey step_key(const HdModel* m, const HdModel::Lane& ln) {
     k.gallow = k.o.guide != GUIDE_NONE ? ln.ws.gallow : nullptr;
     k.gbias = k.o.guide == GUIDE_ALLOW_BIAS ? ln.ws.gbias : nullptr;
     if (k.o.budget) { k.borigin = ln.ws.borigin; k.bmax = ln.ws.bmax; k.bn = ln.ws.bn; }
+    if (k.o.cmax > 0.f) { k.tfilled = ln.ws.tfilled; k.tcnt = ln.ws.tcnt; k.tfwd = ln.ws.tfwd; }
     return k;
 }
 
 extern "C" HdStatus hd_sample_run(HdModel* m, int32_t t0, int32_t t1) {
     if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_run: no open session");
     if (t0 < 0 || t1 < t0 || t1 > m->sTmax) return fail(HD_ERR_INVALID, "hd_sample_run: steps [%d,%d) outside [0,%d]", t0, t1, m->sTmax);
-    const int K = m->s.K;
+    // a threshold session counts FORWARDS: [t0, t1) are forward numbers, one order position or several each, as the rows decide
+    const int K = m->s.cmax > 0.f ? 1 : m->s.K;
     if (K > 1 && (t0 % K != 0 || (t1 % K != 0 && t1 != m->sTmax)))
         return fail(HD_ERR_INVALID, "hd_sample_run: steps [%d,%d) of a session with %d slots per step: t0 must be a multiple of %d, t1 a multiple or Tmax = %d",
                     t0, t1, K, K, m->sTmax);
@@ -2541,6 +2608,37 @@ extern "C" HdStatus hd_sample_tokens(HdModel* m, int32_t* tokens) {
     return HD_OK;
 }
 
+// include/hudiff_hip.h "confidence threshold": chunks of forwards until every row is full (or Tmax forwards have run), one small
+// read-back and one synchronisation per chunk.
+extern "C" HdStatus hd_sample_run_to_end(HdModel* m, int32_t chunk, int32_t* forwards) {
+    if (forwards) *forwards = 0;
+    if (!m || !m->in_session) return fail(HD_ERR_STATE, "hd_sample_run_to_end: no open session");
+    if (!(m->s.cmax > 0.f)) return fail(HD_ERR_STATE, "hd_sample_run_to_end: the session has no confidence threshold (hd_set_confidence)");
+    if (m->sB == 0 || m->sTmax == 0) { m->ran_to_end = true; m->end_chunk = 1; return HD_OK; }
+    if (chunk < 1 || chunk > m->sTmax) return fail(HD_ERR_INVALID, "hd_sample_run_to_end: chunk = %d outside [1, Tmax = %d]", chunk, m->sTmax);
+    HIP_TRY(hipSetDevice(m->device));
+    m->ran_to_end = true; m->end_chunk = chunk;
+    std::vector<int32_t> filled((size_t)m->sB), cnt((size_t)m->sB);
+    int n = 0;
+    for (int f = m->s_steps; f < m->sTmax;) {
+        const int f1 = f + chunk < m->sTmax ? f + chunk : m->sTmax;
+        HD_TRY(hd_sample_run(m, f, f1));
+        n += f1 - f;
+        f = f1;
+        for (int l = 0; l < m->nlanes; ++l) {
+            HdModel::Lane& ln = m->lane[l];
+            HIP_TRY(hipMemcpyAsync(filled.data() + ln.row_off, ln.ws.tfilled, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+            HIP_TRY(hipMemcpyAsync(cnt.data() + ln.row_off, ln.ws.tcnt, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+        }
+        HD_TRY(check_guards(m, m->nlanes, nullptr)); // (waits for the lanes; a guard that fired marks the steps invalid, as in hd_sync)
+        bool full = true;
+        for (int b = 0; b < m->sB && full; ++b) full = filled[b] + cnt[b] >= m->sT[b];
+        if (full) break;
+    }
+    if (forwards) *forwards = n;
+    return HD_OK;
+}
+
 static HdStatus sample_end_impl(HdModel* m, int32_t* tokens, bool* numeric) {
     HIP_TRY(hipSetDevice(m->device));
     HD_TRY(sample_collect(m, tokens, numeric));
@@ -2550,10 +2648,15 @@ static HdStatus sample_end_impl(HdModel* m, int32_t* tokens, bool* numeric) {
     // handle stays on them.  At most one repeat per guard.
     for (int attempt = 0; m->s_dirty && attempt < 2; ++attempt) {
         const int steps = m->s_steps;
+        // a threshold session that was run to its end is run to its end again: on other kernels its keys differ in the last bits, and
+        // with them, possibly, the number of forwards its rows need
+        const bool to_end = m->ran_to_end;
+        const int chunk = m->end_chunk;
         m->s_dirty = false;                          // (hd_sample_restart would otherwise look at the same flags again)
         m->s_steps = 0;
         HD_TRY(hd_sample_restart(m, m->s_seed));
-        if (steps > 0) HD_TRY(hd_sample_run(m, 0, steps));
+        if (to_end) HD_TRY(hd_sample_run_to_end(m, chunk, nullptr));
+        else if (steps > 0) HD_TRY(hd_sample_run(m, 0, steps));
         HD_TRY(sample_collect(m, tokens, numeric));
         m->last_call_repeated = true;
     }
@@ -2650,7 +2753,8 @@ extern "C" HdStatus hd_sample(HdModel* m, int32_t* tokens, const int32_t* region
         tmax_eff = (tmax_eff + m->s.K - 1) / m->s.K * m->s.K;
         if (tmax_eff > Tmax) tmax_eff = Tmax;
     }
-    HdStatus s = hd_sample_run(m, 0, tmax_eff);
+    // a threshold session runs until its rows are full, looking every 4 forwards
+    HdStatus s = m->s.cmax > 0.f ? hd_sample_run_to_end(m, Tmax < 4 ? (Tmax > 0 ? Tmax : 1) : 4, nullptr) : hd_sample_run(m, 0, tmax_eff);
     if (s != HD_OK) { m->in_session = false; m->cl = 0; return s; }
     return hd_sample_end(m, tokens);
 }
@@ -2722,12 +2826,57 @@ extern "C" HdStatus hd_sample_order(HdModel* m, int32_t* order) {
     return readback_done(m, "hd_sample_order", "order is");
 }
 
+// include/hudiff_hip.h "confidence threshold": the progress of every row, the forward number of every position, and the keys of the
+// last forward run (any confident session).
+extern "C" HdStatus hd_sample_progress(HdModel* m, int32_t* filled) {
+    if (!m || (!m->in_session && !m->order_ready)) return fail(HD_ERR_STATE, "hd_sample_progress: no session (open, or ended and not yet replaced)");
+    if (!(m->s.cmax > 0.f)) return fail(HD_ERR_STATE, "hd_sample_progress: the session has no confidence threshold (hd_set_confidence)");
+    if (m->sB == 0) return HD_OK;
+    if (!filled) return fail(HD_ERR_INVALID, "hd_sample_progress: null filled");
+    HIP_TRY(hipSetDevice(m->device));
+    std::vector<int32_t> cnt((size_t)m->sB);
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(filled + ln.row_off, ln.ws.tfilled, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+        HIP_TRY(hipMemcpyAsync(cnt.data() + ln.row_off, ln.ws.tcnt, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+    }
+    const HdStatus s = readback_done(m, "hd_sample_progress", "progress is");
+    for (int b = 0; b < m->sB; ++b) filled[b] += cnt[b];       // start of the last forward + what it took
+    return s;
+}
+
+extern "C" HdStatus hd_sample_forwards(HdModel* m, int32_t* fwd) {
+    if (!m || (!m->in_session && !m->order_ready)) return fail(HD_ERR_STATE, "hd_sample_forwards: no session (open, or ended and not yet replaced)");
+    if (!(m->s.cmax > 0.f)) return fail(HD_ERR_STATE, "hd_sample_forwards: the session has no confidence threshold (hd_set_confidence)");
+    if (m->sB == 0 || m->sTmax == 0) return HD_OK;
+    if (!fwd) return fail(HD_ERR_INVALID, "hd_sample_forwards: null fwd");
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(fwd + (size_t)ln.row_off * m->sTmax, ln.ws.tfwd, (size_t)ln.B * m->sTmax * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+    }
+    return readback_done(m, "hd_sample_forwards", "forward numbers are");
+}
+
+extern "C" HdStatus hd_sample_keys(HdModel* m, float* conf) {
+    if (!m || (!m->in_session && !m->order_ready)) return fail(HD_ERR_STATE, "hd_sample_keys: no session (open, or ended and not yet replaced)");
+    if (m->s.policy != HD_SLOTS_CONFIDENT) return fail(HD_ERR_STATE, "hd_sample_keys: the session does not choose its slots (hd_set_slot_policy)");
+    if (m->sB == 0 || m->sTmax == 0) return HD_OK;
+    if (!conf) return fail(HD_ERR_INVALID, "hd_sample_keys: null conf");
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(conf + (size_t)ln.row_off * m->sTmax, ln.ws.conf, (size_t)ln.B * m->sTmax * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
+    }
+    return readback_done(m, "hd_sample_keys", "keys are");
+}
+
 extern "C" HdStatus hd_score(HdModel* m, const int32_t* tokens, const int32_t* region, const int32_t* chain,
                              const int32_t* order, const int32_t* T, int32_t B, int32_t Tmax, uint32_t flags,
                              uint64_t seed, uint64_t row0, const uint8_t* enc_masks, const uint8_t* conv_masks, float* logp) {
     if (m && !logp && B > 0 && Tmax > 0) return fail(HD_ERR_INVALID, "hd_score: null logp");
     HD_TRY(hd_score_begin(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, enc_masks, conv_masks));
-    HdStatus s = hd_sample_run(m, 0, Tmax);
+    HdStatus s = m->s.cmax > 0.f ? hd_sample_run_to_end(m, Tmax < 4 ? (Tmax > 0 ? Tmax : 1) : 4, nullptr) : hd_sample_run(m, 0, Tmax);
     if (s != HD_OK) { m->in_session = false; m->cl = 0; return s; }
     std::vector<int32_t> filled((size_t)B * m->L + 1);
     s = hd_sample_end(m, filled.data());

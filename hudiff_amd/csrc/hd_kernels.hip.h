@@ -2506,11 +2506,28 @@ __device__ __forceinline__ BudgetAt budget_at(const BudgetP& bu, int b, int L, i
     const int o = bu.origin[(long)b * L + slot];
     return BudgetAt{o, (o <= 21 && bu.n[b] >= bu.max_mut[b]) ? o : -1};
 }
+// THRESHOLD (run time; hd_set_confidence, include/hudiff_hip.h "confidence threshold"): a second nullable pointer group, so no further
+// instantiation either.  A threshold session is a confident one and always runs the GUIDED form.  Per row the device keeps where the
+// last forward started, `filled`, and how many positions it took, `cnt`; n = filled + cnt is where the next one starts.  slot_select_k
+// is the one writer of both (it stores filled = n and the new cnt at the start of a forward); slot_conf_k in front of it forms the same
+// sum read-only and the draw behind it reads the stored pair.  The launch boundaries keys -> selection -> draw are the ordering.
+struct ThreshP {
+    int32_t* filled;         // [B]: order position at which the row's last forward started; nullptr = the session has no threshold
+    int32_t* cnt;            // [B]: positions that forward took
+    int32_t* fwd;            // [B, Tmax]: forward number that drew position t, -1 where nothing was drawn
+    float cmax;              // 1 / tau: a key qualifies iff c <= cmax
+};
+// where the next forward of row b starts: its progress so far, at most Tb
+__device__ __forceinline__ int thresh_next(const ThreshP& th, int b, int Tb) {
+    const int n = th.filled[b] + th.cnt[b];
+    return n < Tb ? n : Tb;
+}
 struct GuideP {
     const uint32_t* allow;   // [B, Tmax] of the lane, gathered by step on the host (as `target`): bit j allows token j
     const float* bias;       // [B, Tmax, 22] or nullptr
     float temperature;       // 0 = greedy
     BudgetP bud;             // mutation budget; origin == nullptr: none
+    ThreshP th;              // confidence threshold; filled == nullptr: none
 };
 enum { DRAW_SAMPLE = 0, DRAW_RECORD = 1, DRAW_SCORE = 2 };
 
@@ -2683,6 +2700,8 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
 // logp / target: [B, Tmax] of the lane (row b at step t); read and written by the recording and the teacher-forced modes only.
 // Nine instantiations: three modes x {plain, guided, guided + truncation}.  The guide argument is GuideP when GUIDED, GuideTP (the three
 // cut parameters behind the guide) when TRUNC, and an empty struct otherwise.  A mutation budget rides in GuideP (BudgetP) and adds none.
+// Nor does a confidence threshold (ThreshP in GuideP, guided forms only): workgroup (b, j) is then active iff j < cnt[b], at position
+// t = filled[b] + j, stores fwd[b, t] = step, and the last workgroup advances the step -- the forward number -- by 1.
 constexpr int SS_WAVES = 16;
 struct NoGuide {};
 template <bool GUIDED, bool TRUNC> using DrawGuideArg = std::conditional_t<GUIDED, GuideArg<TRUNC>, NoGuide>;
@@ -2699,8 +2718,21 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __re
     __shared__ float lg[32];
     const int b = blockIdx.x;
     const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t t = step + blockIdx.y;
-    if ((int)t < T[b]) {                                 // (T[b] <= Tmax: checked by the begin)
+    uint32_t t = step + blockIdx.y;
+    [[maybe_unused]] bool thresh = false, idle = false;
+    if constexpr (GUIDED) {
+        // a threshold session: `step` is the forward number, and row b fills the cnt[b] positions from filled[b] on (slot_select_k has
+        // stored both for this forward; cnt <= T[b] - filled, and 0 for a finished row)
+        const ThreshP* th;
+        if constexpr (TRUNC) th = &ga.g.th; else th = &ga.th;
+        if (th->filled) {
+            thresh = true;
+            t = (uint32_t)th->filled[b] + blockIdx.y;
+            idle = (int)blockIdx.y >= th->cnt[b];
+            if (!idle && threadIdx.x == 0) th->fwd[(long)b * Tmax + t] = (int32_t)step;
+        }
+    }
+    if (!idle && (int)t < T[b]) {                        // (T[b] <= Tmax: checked by the begin)
         const long bt = (long)b * Tmax + t;
         const int slot = order[bt];
         const float* x = Hm + (compact ? (long)b : (long)sg.row(b, slot)) * D;
@@ -2724,7 +2756,7 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __re
         __threadfence();
         if (atomicAdd(&rs->done, 1u) == gridDim.x * gridDim.y - 1) {
             __hip_atomic_store(&rs->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&rs->step, step + gridDim.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&rs->step, step + (thresh ? 1u : gridDim.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -2755,7 +2787,12 @@ __global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __rest
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int Tb = T[b];                                 // (0 <= T[b] <= Tmax: checked by the begin)
     const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int n = step < (uint32_t)Tb ? (int)step : Tb;
+    int n = step < (uint32_t)Tb ? (int)step : Tb;
+    if constexpr (GUIDED) {                              // a threshold session: the row's own progress, not the step
+        const ThreshP* th;
+        if constexpr (TRUNC) th = &ga.g.th; else th = &ga.th;
+        if (th->filled) n = thresh_next(*th, b, Tb);
+    }
     const int i0 = blockIdx.x * SC_WAVES;
     if (i0 >= Tb || i0 + SC_WAVES <= n) return;          // (the whole workgroup: nothing below is reached by a part of it)
     const int i = i0 + wave;
@@ -2807,22 +2844,31 @@ __global__ void __launch_bounds__(64 * SC_WAVES) slot_conf_k(const float* __rest
 // are at most L <= 304 of them).  Keys go to LDS, a key that is not a finite positive number becomes +inf (behind every finite one),
 // every thread counts the (c, i) pairs smaller than its own -- its rank -- and the min(K, remaining) smallest move to the front in
 // rank order; the others follow in their previous relative order.  Each thread holds its own entry (slot, target, guide) in registers
-// across the barriers, so every read of the row is done before the first write.
+// across the barriers, so every read of the row is done before the first write.  With a threshold (ThreshP, nullable) the number that
+// move is min(K, remaining, max(1, qualifying keys)) and the row's progress is kept here.
 constexpr int SEL_THREADS = 320;
 template <bool GUIDED>
 __global__ void __launch_bounds__(SEL_THREADS) slot_select_k(int32_t* __restrict__ order, int32_t* __restrict__ target,
                                                    const int32_t* __restrict__ T, int Tmax, int K,
                                                    const RunState* __restrict__ rs, const float* __restrict__ conf,
-                                                   [[maybe_unused]] uint32_t* __restrict__ gallow, [[maybe_unused]] float* __restrict__ gbias) {
+                                                   [[maybe_unused]] uint32_t* __restrict__ gallow, [[maybe_unused]] float* __restrict__ gbias,
+                                                   ThreshP th) {
     __shared__ float key[SEL_THREADS];
     __shared__ int front[SEL_THREADS];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int Tb = T[b];
     const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int n = step < (uint32_t)Tb ? (int)step : Tb;
+    int n = step < (uint32_t)Tb ? (int)step : Tb;
+    if (th.filled) {
+        // a threshold session: the row's own progress.  This kernel is the one writer of (filled, cnt): every thread reads the pair of the
+        // last forward here, and thread 0 stores this forward's behind a barrier (a finished row: cnt = 0, so the draw leaves it alone)
+        n = thresh_next(th, b, Tb);
+        __syncthreads();
+        if (Tb - n <= 0 && tid == 0) { th.filled[b] = n; th.cnt[b] = 0; }
+    }
     const int N = Tb - n;
     if (N <= 0 || N > SEL_THREADS) return;               // (N <= L <= 304: the begin rejects a list that repeats a slot)
-    const int k = K < N ? K : N;
+    int k = K < N ? K : N;
     const bool live = tid < N;
     const long p0 = (long)b * Tmax + n;
     float c = INFINITY;
@@ -2844,9 +2890,20 @@ __global__ void __launch_bounds__(SEL_THREADS) slot_select_k(int32_t* __restrict
     }
     key[tid] = c;
     __syncthreads();
-    int r = 0;
+    // the qualifying count q of a threshold session rides in the ranking loop: every live thread forms the same q from the same keys
+    // (+inf never qualifies), so there is no further barrier and no atomic; cnt = min(K, N, max(1, q))
+    int r = 0, q = 0;
     if (live)
-        for (int u = 0; u < N; ++u) { const float cu = key[u]; r += (cu < c || (cu == c && u < tid)) ? 1 : 0; }
+        for (int u = 0; u < N; ++u) {
+            const float cu = key[u];
+            r += (cu < c || (cu == c && u < tid)) ? 1 : 0;
+            q += (cu < INFINITY && cu <= th.cmax) ? 1 : 0;
+        }
+    if (th.filled && live) {
+        q = q < 1 ? 1 : q;
+        k = q < k ? q : k;
+        if (tid == 0) { th.filled[b] = n; th.cnt[b] = k; }
+    }
     front[tid] = (live && r < k) ? 1 : 0;
     __syncthreads();
     if (!live) return;

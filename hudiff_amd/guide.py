@@ -269,6 +269,51 @@ def confidence_keys(logits, allow=None, bias=None, temperature=1.0, truncation=N
         return np.where(good, np.log(np.where(good, c, 1.0)), np.inf)
 
 
+def confidence_tau(tau):
+    """A confidence threshold as the library takes it: a finite float in [0, 1] (0 = none); anything else is a ValueError."""
+    if isinstance(tau, (bool, str, bytes)) or tau is None:
+        raise ValueError(f"confidence must be a number in [0, 1], got {tau!r}")
+    try:
+        t = float(tau)
+    except (TypeError, ValueError):
+        raise ValueError(f"confidence must be a number in [0, 1], got {tau!r}") from None
+    if not (np.isfinite(t) and 0.0 <= t <= 1.0):
+        raise ValueError(f"confidence must be finite and in [0, 1], got {tau!r}")
+    return t
+
+
+def confidence_cmax(tau):
+    """The kernel argument of a confidence threshold (include/hudiff_hip.h "confidence threshold"): cmax = 1.0f / tau, one float32
+    division of the float32 tau -- a key c = 1 / p_max qualifies iff c <= cmax.  tau in (0, 1]."""
+    t = confidence_tau(tau)
+    if t == 0.0:
+        raise ValueError("confidence 0 means no threshold: there is no cmax")
+    with np.errstate(over="ignore"):
+        return np.float32(1.0) / np.float32(t)
+
+
+def threshold_select(c32, K, cmax):
+    """Steps 2 to 4 of include/hudiff_hip.h "confidence threshold" in numpy float32: c32 float32 [N] are the keys of the N >= 1
+    remaining positions of one row, in list order; K the cap; cmax float32.  A key that is not a finite positive number becomes +inf;
+    q = the keys with c <= cmax (an infinite one never qualifies); cnt = min(K, N, max(1, q)); the cnt smallest (c, i), compared
+    lexicographically, are chosen.  Returns ``(chosen, cnt, perm)``: int64 [cnt], the chosen positions in rank order; the count; int64
+    [N], the whole permutation -- new position r holds old position perm[r]: the chosen ones, then the others in their previous
+    relative order."""
+    c = np.array(c32, dtype=np.float32).reshape(-1)
+    N, K = c.size, int(K)
+    if N < 1 or K < 1:
+        raise ValueError(f"threshold_select needs at least one key and K >= 1, got N = {N}, K = {K}")
+    cmax = np.float32(cmax)
+    with np.errstate(invalid="ignore"):
+        c = np.where((c > 0) & (c < np.inf), c, np.float32(np.inf)).astype(np.float32)      # (NaN compares false)
+        q = int(np.count_nonzero((c < np.inf) & (c <= cmax)))
+    cnt = min(K, N, max(1, q))
+    rank = np.argsort(c, kind="stable")              # a stable sort keeps list order among equal keys
+    chosen = rank[:cnt].astype(np.int64)
+    rest = np.setdiff1d(np.arange(N), chosen)        # (sorted: the previous relative order)
+    return chosen, cnt, np.concatenate([chosen, rest]).astype(np.int64)
+
+
 def beam_select(cand, width):
     """Step 3 of include/hudiff_hip.h "beam search" in numpy: cand float32 [W, 22] is the candidate table of one group,
     cand[w, j] = score[w] + lp[w, j].  The candidates (w, j) are ranked by cand descending, ties to the smaller (w, j) compared

@@ -29,6 +29,12 @@ def _get(cfg, key, default=None):
     return getattr(cfg, key, default)
 
 
+def _tau(confidence):
+    """A confidence threshold as hd_set_confidence takes it (ValueError outside [0, 1])."""
+    from .guide import confidence_tau
+    return confidence_tau(confidence)
+
+
 def _to_numpy(x):
     if x is None:
         return None, False
@@ -330,18 +336,61 @@ class _Denoiser:
         L.check(self._lib.hd_mutation_count(self._h, L.ptr(n, C.c_int32)))
         return n
 
-    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None, budget=None):
+    # -- confidence threshold ----------------------------------------------------------------------
+    def set_confidence(self, tau):
+        """hd_set_confidence: the confidence threshold tau in (0, 1] (0 clears) of the NEXT sample / sample_begin / score / score_begin
+        on this handle, which consumes it whether it succeeds or fails (include/hudiff_hip.h "confidence threshold")."""
+        L.check(self._lib.hd_set_confidence(self._h, _tau(tau)))
+
+    def sample_progress(self, B=None):
+        """hd_sample_progress: int32 [B], the order positions every row of the open threshold session has filled, or of the last one."""
+        B = self._session_B if B is None else B
+        filled = np.zeros(B, dtype=np.int32)
+        L.check(self._lib.hd_sample_progress(self._h, L.ptr(filled, C.c_int32)))
+        return filled
+
+    def sample_forwards(self, B=None, Tmax=None):
+        """hd_sample_forwards: int32 [B, Tmax], the forward number that drew every order position of the threshold session (open, or
+        the last one); -1 where nothing was drawn."""
+        B = self._session_B if B is None else B
+        Tmax = self._session_Tmax if Tmax is None else Tmax
+        fwd = np.full((B, Tmax), -1, dtype=np.int32)
+        L.check(self._lib.hd_sample_forwards(self._h, L.ptr(fwd, C.c_int32)))
+        return fwd
+
+    def sample_keys(self, B=None, Tmax=None):
+        """hd_sample_keys: float32 [B, Tmax], the keys c = 1 / p_max of the last forward of a confident session (with or without a
+        threshold), by order position as the order stood BEFORE that forward's permutation; meaningful for the positions that were
+        still to fill in that forward."""
+        B = self._session_B if B is None else B
+        Tmax = self._session_Tmax if Tmax is None else Tmax
+        conf = np.zeros((B, Tmax), dtype=np.float32)
+        L.check(self._lib.hd_sample_keys(self._h, L.ptr(conf, C.c_float)))
+        return conf
+
+    def sample_run_to_end(self, chunk=4):
+        """hd_sample_run_to_end: runs the open threshold session in chunks of ``chunk`` forwards, looking at the rows' progress after
+        each, until every row is full (or Tmax forwards have run); returns the number of forwards it enqueued."""
+        n = C.c_int32()
+        L.check(self._lib.hd_sample_run_to_end(self._h, int(chunk), C.byref(n)))
+        return int(n.value)
+
+    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None, budget=None, confidence=None):
         """What the next begin consumes: the block size (the library is told only when it is not 1), the slot policy (told only when
-        it is not "given"), the truncation (told only when it cuts something), the budget (told only when there is one) and the
-        guide."""
+        it is not "given"), the truncation (told only when it cuts something), the budget (told only when there is one), the
+        confidence threshold (told only when there is one) and the guide."""
         policy = self._policy_id(slot_policy)
         block = int(slots_per_step) != 1
         trunc = truncation is not None and not truncation.neutral
+        tau = None if confidence is None else _tau(confidence)
+        thresh = tau is not None and tau != 0.0
         if block:
             self.set_slots_per_step(slots_per_step)
         try:
             if policy != L.HD_SLOTS_GIVEN:
                 L.check(self._lib.hd_set_slot_policy(self._h, policy))
+            if thresh:
+                L.check(self._lib.hd_set_confidence(self._h, tau))
             if trunc:
                 self.set_truncation(truncation)
             if budget is not None:
@@ -357,11 +406,13 @@ class _Denoiser:
                 self._lib.hd_set_truncation(self._h, None)
             if budget is not None:
                 self._lib.hd_set_budget(self._h, None)
+            if thresh:
+                self._lib.hd_set_confidence(self._h, 0.0)
             raise
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1,
-               slot_policy="given", truncation=None, budget=None):
+               slot_policy="given", truncation=None, budget=None, confidence=None):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
@@ -382,13 +433,18 @@ class _Denoiser:
         of its origin-bearing slots draws its origin from then on (include/hudiff_hip.h "mutation budget"); ``mutation_count()``
         afterwards returns what every row spent.  One slot per forward only.
 
+        ``confidence``: a threshold tau in (0, 1] for this call only, with ``slot_policy="confident"``: every forward fills, per row,
+        all remaining slots whose top probability is at least tau -- at least one, at most ``slots_per_step`` -- so the number of
+        forwards follows the model's certainty (include/hudiff_hip.h "confidence threshold"); ``sample_forwards()`` afterwards returns
+        the forward that drew every position.  None or 0 = no threshold.
+
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
         are the same with and without it."""
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
-        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
@@ -499,9 +555,9 @@ class _Denoiser:
 
     # -- likelihood of given sequences -------------------------------------------------------------
     def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given",
-                   truncation=None, budget=None):
+                   truncation=None, budget=None, confidence=None):
         logp = np.zeros((B, Tmax), dtype=np.float32)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_score(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
@@ -511,7 +567,7 @@ class _Denoiser:
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given",
-              truncation=None, budget=None):
+              truncation=None, budget=None, confidence=None):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -536,6 +592,10 @@ class _Denoiser:
         library picks the visiting order (``sample_order()`` afterwards) and logp[b, t] belongs to position t of THAT order.  The slot
         of step t depends on the steps before it, so there is no step-parallel form: ``parallel=True`` raises, None runs the loop.
 
+        ``confidence``: teacher-forced under the threshold sampler (needs ``slot_policy="confident"``; ``slots_per_step`` is the cap):
+        the library picks order and forwards by the same rule (``sample_order()`` / ``sample_forwards()`` afterwards).  No
+        step-parallel form.
+
         ``budget``: the values are log-probabilities under the budgeted sampler (hudiff_amd.guide.Budget): at a position where the row
         has spent its budget the origin scores 0 and any other token -inf (no error).  Whether a position is exhausted depends on the
         steps before it, so there is no step-parallel form either."""
@@ -545,6 +605,11 @@ class _Denoiser:
             if parallel:
                 raise ValueError("step-parallel scoring cannot follow a mutation budget: whether step t is exhausted depends on the "
                                  "steps before it; use parallel=False (or None)")
+            parallel = False
+        if confidence is not None and _tau(confidence) != 0.0:
+            if parallel:
+                raise ValueError("step-parallel scoring cannot follow a confidence threshold: the slots of a forward depend on the "
+                                 "forwards before it; use parallel=False (or None)")
             parallel = False
         if confident and parallel:
             raise ValueError("step-parallel scoring cannot follow slot_policy='confident': the slot of step t depends on the steps "
@@ -558,7 +623,8 @@ class _Denoiser:
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
         flags = self._flags(dropout, graph, prune, lanes)
         if not parallel:
-            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy, truncation, budget)
+            logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy, truncation, budget,
+                                   confidence)
         else:
             from . import scoring
             x = scoring.expand_steps(tok, reg, chn, order, T, slots_per_step=K)      # (K outside [1, 64]: ValueError)
@@ -585,11 +651,11 @@ class _Denoiser:
         return logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None, budget=None):
+                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None, budget=None, confidence=None):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
         last_run_ms / sample_logp work on it as on a sampling session."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                          self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
@@ -598,10 +664,10 @@ class _Denoiser:
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                      enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1,
-                     slot_policy="given", truncation=None, budget=None):
+                     slot_policy="given", truncation=None, budget=None, confidence=None):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
@@ -610,7 +676,7 @@ class _Denoiser:
 
     def sample_run(self, t0, t1):
         """hd_sample_run: order positions [t0, t1); in a session with K slots per step t0 is a multiple of K and t1 a multiple of K
-        or Tmax, and ceil((t1 - t0) / K) forwards are enqueued."""
+        or Tmax, and ceil((t1 - t0) / K) forwards are enqueued.  A threshold session takes forward numbers: t1 - t0 forwards."""
         L.check(self._lib.hd_sample_run(self._h, int(t0), int(t1)))
 
     def sample_restart(self, seed):

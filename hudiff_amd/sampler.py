@@ -58,7 +58,8 @@ def _id_runs(gids: np.ndarray, max_rows: int):
 def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes: int = 1,
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
                 job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1,
-                slot_policy: str = "given", return_order: bool = False, truncation=None, max_mutations: Optional[int] = None):
+                slot_policy: str = "given", return_order: bool = False, truncation=None, max_mutations: Optional[int] = None,
+                confidence: Optional[float] = None, forward_stats: Optional[dict] = None):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -84,6 +85,11 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     ``max_mutations``: a mutation budget (model.sample ``budget=``): every row may differ from its job's ``origin`` in at most that many
     of the slots it samples, counted anew in every pass; None passes nothing on and the calls into the library are exactly today's.
 
+    ``confidence``: a threshold tau in (0, 1] under ``slot_policy="confident"`` (model.sample): a forward fills every remaining slot
+    of a row whose top probability is at least tau -- at least one, at most ``slots_per_step``; None or 0 passes nothing on and the
+    calls into the library are exactly today's.  ``forward_stats``: a dict that then receives, summed over this rank's rows with
+    slots to fill, ``rows``, ``forwards`` (their total) and ``max`` (the most any row needed).
+
     ``return_order``: also returns (last) int32 [len(jobs), passes, replicas, Tmax], the order each row took (model.sample_order;
     under "given" the order it was handed), gathered like the log-probabilities."""
     if slot_policy not in ("given", "confident"):
@@ -104,6 +110,9 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
         more["slot_policy"] = slot_policy
     if truncation is not None and not truncation.neutral:
         more["truncation"] = truncation
+    thresh = confidence is not None and float(confidence) != 0.0
+    if thresh:
+        more["confidence"] = float(confidence)
     od = np.zeros((passes, hi - lo, Tmax), np.int32) if return_order else None
     jid = np.arange(len(jobs), dtype=np.int64) if job_ids is None else np.asarray(job_ids, dtype=np.int64)
     pos = np.arange(lo, hi)                                      # positions in the packed (job-major) row list
@@ -134,6 +143,11 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
             out[p, s - lo:e - lo] = tok
             if return_order:
                 od[p, s - lo:e - lo] = model.sample_order(len(jb), Tmax)
+            if thresh and forward_stats is not None:
+                need = model.sample_forwards(len(jb), Tmax).max(axis=1)[T > 0] + 1        # (the last forward that drew in the row)
+                forward_stats["rows"] = forward_stats.get("rows", 0) + int(need.size)
+                forward_stats["forwards"] = forward_stats.get("forwards", 0) + int(need.sum())
+                forward_stats["max"] = max(forward_stats.get("max", 0), int(need.max()) if need.size else 0)
     gathered = [D.gather_rows(out[p], n_rows, L, all_ranks) for p in range(passes)]
     # (the float32 bits of the log-probabilities travel as int32 through the same gather)
     gathered_lp = [D.gather_rows(lp[p].view(np.int32), n_rows, Tmax, all_ranks) for p in range(passes)] if return_logp else None
@@ -249,7 +263,8 @@ def noise_in_reference_order(q_flat, jobs: Sequence[Job], replicas: int) -> np.n
 def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int, *, want: int, tries: int, accept,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
                            logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1,
-                           slot_policy: str = "given", truncation=None, max_mutations: Optional[int] = None) -> List[List[np.ndarray]]:
+                           slot_policy: str = "given", truncation=None, max_mutations: Optional[int] = None,
+                           confidence: Optional[float] = None, forward_stats: Optional[dict] = None) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -268,7 +283,9 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
     ``truncation``: as in ``sample_jobs``, for every sweep.
 
     ``max_mutations``: as in ``sample_jobs``; every sweep redraws every sampled slot and counts from 0, so every row written differs from
-    its job's ``origin`` in at most that many of them."""
+    its job's ``origin`` in at most that many of them.
+
+    ``confidence``, ``forward_stats``: as in ``sample_jobs``, for every sweep."""
     state = [{"left": want, "tries": tries, "tokens": None, "out": []} for _ in jobs]
     active = [j for j in range(len(jobs)) if want > 0 and tries > 0]
     sweep = 0
@@ -289,6 +306,9 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
             more["truncation"] = truncation
         if max_mutations is not None:
             more["max_mutations"] = max_mutations
+        if confidence is not None and float(confidence) != 0.0:
+            more["confidence"] = confidence
+            more["forward_stats"] = forward_stats
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:

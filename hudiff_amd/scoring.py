@@ -132,7 +132,7 @@ def draw_orders(loc, orders: int, seed: int, job_id: int) -> np.ndarray:
 
 def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout: str = "off", parallel=None,
                device_batch: int = 256, all_ranks: bool = False, job_ids: Optional[Sequence[int]] = None, slots_per_step: int = 1,
-               slot_policy: str = "given", truncation=None):
+               slot_policy: str = "given", truncation=None, confidence: Optional[float] = None):
     """Score every job along ``orders`` random visiting orders of its ``loc``.
 
     ``truncation``: a hudiff_amd.guide.Truncation -- the scores are under the truncated sampler (model.score); a token its step's cut
@@ -141,6 +141,9 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
     ``slot_policy`` = "confident" scores under the confident sampler (model.score): the order is the model's own, found teacher-forced
     from the candidate list ``loc`` as it stands (only ties ever see the list), so ``orders`` must be 1, the sequential loop runs
     (``parallel=True`` is a ValueError) and ``order`` in the result is the order taken.  With "given" nothing is passed on.
+
+    ``confidence``: a threshold tau in (0, 1] under ``slot_policy="confident"``: the scores are under the threshold sampler
+    (model.score), ``slots_per_step`` being its cap; None or 0 passes nothing on.
 
     ``slots_per_step`` = K > 1 scores under the block sampler (model.score); at 1 the calls into the library are the one-slot ones.
 
@@ -174,6 +177,8 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
         more["slot_policy"] = slot_policy
     if truncation is not None and not truncation.neutral:
         more["truncation"] = truncation
+    if confidence is not None and float(confidence) != 0.0:
+        more["confidence"] = float(confidence)
     from .sampler import _id_runs
     pos = np.arange(lo, hi)
     gids = jid[pos // orders] * orders + pos % orders

@@ -61,8 +61,9 @@ extern "C" {
                                  hd_score and the flag HD_RECORD_LOGP; the variant tests added hd_debug_launch_tally; guided sampling added hd_set_guide and
                                  the struct HdGuide; block decoding added hd_set_slots_per_step; the slot policy added hd_set_slot_policy and
                                  hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation; beam search added hd_set_beam and
-                                 hd_beam_state; the mutation budget added hd_set_budget, hd_mutation_count and the struct HdBudget -- entry points only, so the
-                                 version is unchanged */
+                                 hd_beam_state; the mutation budget added hd_set_budget, hd_mutation_count and the struct HdBudget; the confidence
+                                 threshold added hd_set_confidence, hd_sample_run_to_end, hd_sample_progress, hd_sample_forwards and hd_sample_keys -- entry
+                                 points only, so the version is unchanged */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -311,7 +312,8 @@ HdStatus hd_set_slots_per_step(HdModel* m, int32_t k);
  * HD_ERR_UNSUPPORTED.
  *
  * hd_sample_order copies the current order [B, Tmax] of the session out, rows in whole-batch order whatever the lane split: positions
- * < min(steps run, T[b]) are the visited slots in visiting order; in a HD_SLOTS_GIVEN session it is the order that was given.  Legal
+ * < min(steps run, T[b]) -- in a threshold session ("confidence threshold"): positions < filled[b] -- are the visited slots in
+ * visiting order; in a HD_SLOTS_GIVEN session it is the order that was given.  Legal
  * where hd_sample_logp is: inside an open session (it synchronises; HD_ERR_STATE after a guard has fired) and after hd_sample /
  * hd_sample_end until the next begin, hd_forward or hd_destroy.  No session ever opened, or a NULL handle -> HD_ERR_STATE. */
 enum { HD_SLOTS_GIVEN = 0, HD_SLOTS_CONFIDENT = 1 };
@@ -448,6 +450,63 @@ typedef struct HdBudget {
 } HdBudget;
 HdStatus hd_set_budget(HdModel* m, const HdBudget* b);      /* NULL clears */
 HdStatus hd_mutation_count(HdModel* m, int32_t* n /* [B] */);
+
+/* ---- confidence threshold -------------------------------------------------------------------------
+ * A confident session ("slot policy") may carry a threshold tau in (0, 1]: a forward then fills EVERY remaining slot of a row whose top
+ * probability is at least tau -- at least one, at most K (hd_set_slots_per_step, now a cap).  The number of forwards follows the
+ * model's certainty, row by row.  The host forms cmax = 1.0f / tau (one fp32 division); a key c = 1 / p_max qualifies iff c <= cmax.
+ *
+ * State per row, set at the begin and at every hd_sample_restart: filled[b], the positions of order[b, :] already drawn (0); cnt[b], the
+ * count of the last forward (0); fwd[b, t], the forward number that drew position t (-1 where nothing was drawn).
+ *
+ * Forward number f, row b, n = filled[b], N = T[b] - n; a row with N <= 0 is left alone.  Otherwise:
+ *   1. keys c_i of every remaining position i in [n, T[b]) exactly as in "slot policy" (guided, truncated and temperature-0 forms
+ *      included); a key that is not a finite positive number becomes +inf;
+ *   2. q = the number of remaining positions with c_i <= cmax (an fp32 compare; an infinite key never qualifies);
+ *   3. cnt = min(K, N, max(1, q));
+ *   4. the cnt smallest (c_i, i) move to positions n .. n + cnt - 1 in ascending order, the rest follow in their previous relative
+ *      order, targets and guide entries move with their positions: the permutation of "slot policy" with cnt in place of min(K, N);
+ *   5. position t = n + j, j < cnt, is drawn at order[b, t] with the noise, guide, target and logp[b, t] of position t ("block
+ *      decoding"); then fwd[b, t] = f and filled[b] = n + cnt.
+ * Generated dropout masks of forward f are keyed by step = f (a confident K-session keys them by f * K); the Philox counter word of a
+ * draw stays the position t.  A row needs between ceil(T / K) and T forwards; Tmax forwards always finish every row.  All of it runs on
+ * the device inside the captured step, in the launches of a confident session; a threshold session always runs the guided form of the
+ * kernels, as a truncated one does (every bit set, no bias, temperature 1 when no guide is set).
+ *
+ * Running.  hd_sample_run(f0, f1) takes FORWARD NUMBERS in a threshold session: 0 <= f0 <= f1 <= Tmax, no multiple-of-K rule; it
+ * enqueues f1 - f0 forwards without synchronising (each continues from the rows' progress; f names the dropout masks and fwd), and
+ * hd_last_run_ms reports forwards in `steps`.  HD_LOOP_GRAPH works as elsewhere.  hd_sample_run_to_end(chunk, &forwards), legal in
+ * threshold sessions only (HD_ERR_STATE elsewhere; chunk outside [1, Tmax] -> HD_ERR_INVALID), enqueues `chunk` forwards from where the
+ * session stands, reads filled back (one small device-to-host copy and a synchronise; the guards are looked at as in hd_sync), and
+ * repeats until every row has filled[b] == T[b] or Tmax forwards have run; `forwards` (may be NULL) gets the number it enqueued.
+ * hd_sample and hd_score run a threshold session this way with chunk 4.  A guard's repeat in hd_sample_end finishes the rows again:
+ * on the fp32 kernels the keys differ in their last bits and the rows may need a different number of forwards, so a session that was
+ * run to its end is run to its end again by the repeat (any other repeats the same number of forwards).
+ *
+ * Consequences.  With every finite key qualifying (tau <= 1/22, since c <= 22) the session is the confident K-session: order, tokens
+ * and logp agree bit for bit at dropout off, and fwd[b, t] = t / K.  With no key ever qualifying it is the confident 1-session for any
+ * cap K, generated dropout included, and fwd[b, t] = t.  The selection is a deterministic function of the state, so a recording
+ * session's row total is the exact log-likelihood of its tokens under this sampler.  A scoring session consumes the threshold too,
+ * teacher-forced with the same rule: scoring a threshold session's tokens from the same list, K, tau, guide and dropout key reproduces
+ * its order and fwd.
+ *
+ * Read-backs, legal where hd_sample_order is, rows in whole-batch order whatever the lane split, HD_ERR_STATE after a guard has fired
+ * inside the session: hd_sample_progress copies filled [B] out and hd_sample_forwards fwd [B, Tmax] (a session without a threshold ->
+ * HD_ERR_STATE).  hd_sample_keys works for ANY confident session, with or without a threshold: the keys [B, Tmax] of the last forward
+ * run, indexed by order position as the order stood BEFORE that forward's permutation, meaningful for the positions [n, T[b]) of that
+ * forward only (zeros before the first forward) -- the per-slot certainty map of a forward.  A HD_SLOTS_GIVEN session -> HD_ERR_STATE.
+ *
+ * Lifetime: as the block size -- one-shot: the NEXT hd_sample_begin / hd_sample / hd_score_begin / hd_score consumes the threshold
+ * whether it succeeds or fails; hd_sample_restart and the guards' repeats keep it; hd_forward neither uses nor clears it.  tau == 0
+ * clears a threshold not yet consumed.  tau not finite, negative or above 1, or a NULL handle -> HD_ERR_INVALID; inside an open
+ * session -> HD_ERR_STATE.  At the begin: a threshold with HD_SLOTS_GIVEN -> HD_ERR_UNSUPPORTED; with a mutation budget ->
+ * HD_ERR_UNSUPPORTED at any K; a beam is refused by the confident policy already, whose other checks (the candidate list is a set, no
+ * injected dropout) stay. */
+HdStatus hd_set_confidence(HdModel* m, float tau);          /* 0 clears */
+HdStatus hd_sample_run_to_end(HdModel* m, int32_t chunk, int32_t* forwards /* may be NULL */);
+HdStatus hd_sample_progress(HdModel* m, int32_t* filled /* [B] */);
+HdStatus hd_sample_forwards(HdModel* m, int32_t* fwd /* [B, Tmax] */);
+HdStatus hd_sample_keys(HdModel* m, float* conf /* [B, Tmax] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
