@@ -18,6 +18,7 @@ HD_KIND_ANTIBODY, HD_KIND_NANOBODY = 0, 1
 HD_ACT_RELU, HD_ACT_GELU = 1, 2
 HD_DROPOUT_FAITHFUL, HD_DROPOUT_OFF, HD_DROPOUT_INJECT, HD_NO_GRAPH, HD_NO_PRUNE, HD_ONE_LANE, HD_LOOP_GRAPH = 0, 1, 2, 4, 8, 16, 32
 HD_RECORD_LOGP = 64
+HD_RECORD_DIST = 128
 HD_SLOTS_GIVEN, HD_SLOTS_CONFIDENT = 0, 1
 BEAM_MAX_WIDTH = 64
 SLOT_POLICIES = {"given": HD_SLOTS_GIVEN, "confident": HD_SLOTS_CONFIDENT}
@@ -38,6 +39,7 @@ EXPORTS = [
     "hd_set_beam", "hd_beam_state",
     "hd_set_budget", "hd_mutation_count",
     "hd_set_confidence", "hd_sample_run_to_end", "hd_sample_progress", "hd_sample_forwards", "hd_sample_keys",
+    "hd_sample_dist",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -158,6 +160,7 @@ def load():
     lib.hd_sample_progress.argtypes = [vp, i32p]
     lib.hd_sample_forwards.argtypes = [vp, i32p]
     lib.hd_sample_keys.argtypes = [vp, f32p]
+    lib.hd_sample_dist.argtypes = [vp, f32p]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

@@ -116,6 +116,9 @@ struct Workspace {
     // their sum; slot_select_k writes both), and the forward number that drew each position [B, Tmax].  Allocated by the first threshold
     // session of the lane, regrown like the beam's buffers.
     int32_t *tfilled = nullptr, *tcnt = nullptr, *tfwd = nullptr; size_t th_capB = 0, th_capT = 0;
+    // distribution record (HD_RECORD_DIST): the 22 values of every (row, position) a forward drew or scored, [B, Tmax, 22].  Allocated by
+    // the first session of the lane that asks, regrown like the beam's buffers.
+    float* dist = nullptr; size_t dist_cap = 0;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -186,7 +189,8 @@ struct SessionOpts {
     int W = 0;                                       // beam width; 0 = a draw, > 0: beam_cand_k + beam_select_k in its place
     bool budget = false;                             // mutation budget; a budgeted session always draws with the guided kernels (guide != GUIDE_NONE)
     float cmax = 0.f;                                // confidence threshold: 1 / tau (a kernel argument), 0 = none; such a session is confident and guided
-    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget, cmax); }
+    bool dist = false;                               // distribution record (HD_RECORD_DIST of the begin's flags, not an hd_set_*): the draw stores all 22 values
+    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget, cmax, dist); }
     bool operator==(const SessionOpts& o) const { return tied() == o.tied(); }
 };
 
@@ -204,8 +208,10 @@ struct StepKey {
     const uint32_t* gallow = nullptr; const float* gbias = nullptr;     // the guide buffers the launch really reads: when guided / biased
     const int32_t *borigin = nullptr, *bmax = nullptr, *bn = nullptr;   // the budget buffers, when the session has one
     const int32_t *tfilled = nullptr, *tcnt = nullptr, *tfwd = nullptr; // the threshold buffers, when the session has one
+    const float* dist = nullptr;                                        // the distribution record, when the session keeps one
     auto tied() const {
-        return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias, borigin, bmax, bn, tfilled, tcnt, tfwd);
+        return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias, borigin, bmax, bn, tfilled, tcnt, tfwd,
+                        dist);
     }
     bool operator==(const StepKey& k) const { return tied() == k.tied(); }
 };
@@ -1952,6 +1958,7 @@ static HdStatus draw(HdModel* m, const Segs& sg, bool prune) {
     const bool rec = m->s.mode != DRAW_SAMPLE;
     float* logp = rec ? ws.logp : nullptr;
     const int32_t* target = rec ? ws.target : nullptr;
+    float* dist = m->s.dist ? ws.dist : nullptr;         // (a session with the record is a recording or a scoring one: sample_begin_impl)
     const int compact = prune ? 1 : 0;
     const dim3 grid(sg.B, m->s.K), threads(64 * SS_WAVES);
     static_switch<3>(guide_level(m), [&](auto lv) {
@@ -1959,7 +1966,7 @@ static HdStatus draw(HdModel* m, const Segs& sg, bool prune) {
             constexpr int LV = decltype(lv)::value, MODE = decltype(mode)::value;
             const auto guide = [&] { if constexpr (LV == LV_PLAIN) return NoGuide{}; else return guide_arg<LV>(m); }();
             hipLaunchKernelGGL((sample_step_k<MODE, LV != LV_PLAIN, LV == LV_TRUNC>), grid, threads, 0, ln.stream, hm, m->D, m->head, ws.tokens, ws.order,
-                               ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, compact, logp, target, guide);
+                               ws.T, m->sTmax, qn, m->sB, ln.row_off, ln.rs, sg, compact, logp, target, guide, dist);
         });
     });
     HIP_TRY(hipGetLastError());
@@ -2036,6 +2043,9 @@ static HdStatus check_options(const HdModel* m, const BeginIn& in, const Session
                               const HdModel::Budget& budget) {
     const int B = in.B, K = o.K, W = o.W;
     const bool confident = o.policy == HD_SLOTS_CONFIDENT, guided = o.guide != GUIDE_NONE;
+    if (o.dist && W > 0)                             // the distribution record: beam_cand_k + beam_select_k stand in the draw's place
+        return fail(HD_ERR_UNSUPPORTED, "%s: HD_RECORD_DIST with a beam width set (hd_set_beam): a beam session has its candidate table "
+                                        "(hd_beam_state), not a distribution record", in.score ? "hd_score_begin" : "hd_sample_begin");
     if (W > 0) {                                     // beam search: one slot per forward in the given order, no noise, no dropout
         if (in.score) return fail(HD_ERR_UNSUPPORTED, "hd_score_begin: a beam width is set (hd_set_beam); a scoring session has no beam");
         if (K > 1 || confident)
@@ -2234,6 +2244,12 @@ static HdStatus bufs_thresh(Workspace& ws, size_t nB, size_t nT, F&& f) {
     HD_TRY(f(&ws.tfilled, nB)); HD_TRY(f(&ws.tcnt, nB)); HD_TRY(f(&ws.tfwd, nT));
     return HD_OK;
 }
+// The distribution record of a session that asked for it (HD_RECORD_DIST), n = B * Tmax * 22.
+template <typename F>
+static HdStatus bufs_dist(Workspace& ws, size_t n, F&& f) {
+    HD_TRY(f(&ws.dist, n));
+    return HD_OK;
+}
 // Its state at the begin and at a restart: nothing filled, no forward run (fwd = -1 everywhere).
 static HdStatus thresh_reset(HdModel::Lane& ln, int Tmax) {
     Workspace& ws = ln.ws;
@@ -2244,7 +2260,7 @@ static HdStatus thresh_reset(HdModel::Lane& ln, int Tmax) {
 }
 
 // Grows a group: its old buffers are released now, not at the next free_ws, and the lane's graphs go -- a captured step holds the old
-// addresses.  group(f) is one of the five above with its sizes bound.
+// addresses.  group(f) is one of the six above with its sizes bound.
 template <typename G>
 static HdStatus regrow(HdModel::Lane& ln, G&& group) {
     Workspace& ws = ln.ws;
@@ -2315,6 +2331,14 @@ static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, 
         }
         HD_TRY(thresh_reset(ln, Tmax));
     }
+    if (o.dist) {                                        // the lane's rows of the record: zeros where nothing has run (and behind T[b])
+        if (need * 22 > ws.dist_cap) {
+            ws.dist_cap = 0;
+            HD_TRY(regrow(ln, [&](auto f) { return bufs_dist(ws, need * 22, f); }));
+            ws.dist_cap = need * 22;
+        }
+        if (nT > 0) HIP_TRY(hipMemsetAsync(ws.dist, 0, nT * 22 * sizeof(float), ln.stream));
+    }
     if (guided && Tmax > 0) {
         HIP_TRY(hipMemcpyAsync(ws.gallow, gallow.data() + (size_t)off * Tmax, nT * sizeof(uint32_t), hipMemcpyHostToDevice, ln.stream));
         if (biased) HIP_TRY(hipMemcpyAsync(ws.gbias, gbias.data() + (size_t)off * Tmax * 22, nT * 22 * sizeof(float), hipMemcpyHostToDevice, ln.stream));
@@ -2369,7 +2393,8 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     m->logp_ready = false;
     m->order_ready = false;
     m->count_ready = false;
-    o.mode = in.score ? DRAW_SCORE : ((in.flags & HD_RECORD_LOGP) || o.W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
+    o.dist = (in.flags & HD_RECORD_DIST) != 0;       // the distribution record: from the flags, and its sampling session records logp too
+    o.mode = in.score ? DRAW_SCORE : ((in.flags & (HD_RECORD_LOGP | HD_RECORD_DIST)) || o.W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
     // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
     // bias, temperature 1), under which g_j == logit_j bit for bit
     // and so does a budgeted one: the budget rides in the guide argument of the guided kernels
@@ -2460,6 +2485,7 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
         HdModel::Lane& ln = m->lane[l];
         HIP_TRY(hipMemcpyAsync(ln.ws.tokens, ln.ws.tokens0, (size_t)ln.B * m->L * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (m->s.mode != DRAW_SAMPLE && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.logp, 0, (size_t)ln.B * m->sTmax * sizeof(float), ln.stream));
+        if (m->s.dist && m->sTmax > 0) HIP_TRY(hipMemsetAsync(ln.ws.dist, 0, (size_t)ln.B * m->sTmax * 22 * sizeof(float), ln.stream));
         if (m->s.budget) HIP_TRY(hipMemsetAsync(ln.ws.bn, 0, (size_t)ln.B * sizeof(int32_t), ln.stream));      // nothing spent yet
         if (m->s.cmax > 0.f) HD_TRY(thresh_reset(ln, m->sTmax));                                                // nothing filled yet
         if (m->s.W > 0) {                             // beam search: only the first row of every group is live again
@@ -2494,6 +2520,7 @@ static StepKey step_key(const HdModel* m, const HdModel::Lane& ln) {
     k.gbias = k.o.guide == GUIDE_ALLOW_BIAS ? ln.ws.gbias : nullptr;
     if (k.o.budget) { k.borigin = ln.ws.borigin; k.bmax = ln.ws.bmax; k.bn = ln.ws.bn; }
     if (k.o.cmax > 0.f) { k.tfilled = ln.ws.tfilled; k.tcnt = ln.ws.tcnt; k.tfwd = ln.ws.tfwd; }
+    if (k.o.dist) k.dist = ln.ws.dist;
     return k;
 }
 
@@ -2781,6 +2808,21 @@ extern "C" HdStatus hd_sample_logp(HdModel* m, float* logp) {
         HIP_TRY(hipMemcpyAsync(logp + (size_t)ln.row_off * m->sTmax, ln.ws.logp, (size_t)ln.B * m->sTmax * sizeof(float), hipMemcpyDeviceToHost, ln.stream));
     }
     return readback_done(m, "hd_sample_logp", "values are");
+}
+
+// include/hudiff_hip.h "distribution record": all 22 values of every (row, position) a forward drew or scored.
+extern "C" HdStatus hd_sample_dist(HdModel* m, float* dist) {
+    if (!m || (!m->in_session && !m->logp_ready)) return fail(HD_ERR_STATE, "hd_sample_dist: no recording session (open, or ended and not yet replaced)");
+    if (!m->s.dist) return fail(HD_ERR_STATE, "hd_sample_dist: the session keeps no distribution record (HD_RECORD_DIST)");
+    if (m->sB == 0 || m->sTmax == 0) return HD_OK;
+    if (!dist) return fail(HD_ERR_INVALID, "hd_sample_dist: null dist");
+    HIP_TRY(hipSetDevice(m->device));
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        HIP_TRY(hipMemcpyAsync(dist + (size_t)ln.row_off * m->sTmax * 22, ln.ws.dist, (size_t)ln.B * m->sTmax * 22 * sizeof(float), hipMemcpyDeviceToHost,
+                               ln.stream));
+    }
+    return readback_done(m, "hd_sample_dist", "values are");
 }
 
 // include/hudiff_hip.h "beam search": score, parent and the candidate table of the last position run.

@@ -2628,6 +2628,7 @@ template <int NW, int MODE = DRAW_SAMPLE, bool GUIDED = false, bool TRUNC = fals
 __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w, int32_t* __restrict__ tokens, int b, int slot, uint32_t t,
                                            const float* __restrict__ q_noise, int q_rows, int q_off, const RunState* __restrict__ rs, int L,
                                            float* lg, float* __restrict__ logp_out = nullptr, int target = 0,
+                                           [[maybe_unused]] float* __restrict__ dist_out = nullptr,
                                            const uint32_t* __restrict__ g_allow = nullptr, const float* __restrict__ g_bias = nullptr,
                                            float g_temp = 1.f, [[maybe_unused]] const TruncP& tr = TruncP{0, 1.f, 0.f},
                                            [[maybe_unused]] const BudgetAt ba = BudgetAt{22, -1}, [[maybe_unused]] int32_t* n_mut = nullptr) {
@@ -2636,6 +2637,12 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
     if (!draw_dist<NW, GUIDED, TRUNC>(x, D, w, rs, lg, g_allow, g_bias, g_temp, tr, d, ba.force)) return;
     const float mylogit = d.g, mx = d.mx, e = d.e, esum = d.esum;
     [[maybe_unused]] const bool allowed = d.allowed, kept = d.kept, greedy = d.greedy;
+    // the distribution record (HD_RECORD_DIST, include/hudiff_hip.h "distribution record"): lane j < 22 stores token j's value, the three
+    // fp32 operations of logp below in their order, so the entry of the token written holds logp's bits.  Run time, a nullable pointer
+    // (uniform over the block); the DRAW_SAMPLE instantiations contain none of it.
+    if constexpr (MODE != DRAW_SAMPLE) {
+        if (dist_out && lane < 22) dist_out[lane] = (allowed && kept) ? (mylogit - mx) - logf(esum) : -INFINITY;
+    }
     if constexpr (MODE == DRAW_SCORE) {
         const float zt = __shfl(mylogit, target & 31);
         [[maybe_unused]] int kt = 1;
@@ -2698,6 +2705,8 @@ __device__ __forceinline__ void sample_row(const float* x, int D, const HeadW& w
 // The last workgroup of the whole grid to finish stores step + K (every workgroup has read `step` before it increments `done`), which
 // saves the one-thread launch per step that advance_step_k was.
 // logp / target: [B, Tmax] of the lane (row b at step t); read and written by the recording and the teacher-forced modes only.
+// dist: [B, Tmax, 22] of the lane or nullptr (HD_RECORD_DIST), the trailing argument; the same two modes store position t's 22 values at
+// dist + bt * 22 behind one uniform null test, and the three DRAW_SAMPLE instantiations never read the argument.
 // Nine instantiations: three modes x {plain, guided, guided + truncation}.  The guide argument is GuideP when GUIDED, GuideTP (the three
 // cut parameters behind the guide) when TRUNC, and an empty struct otherwise.  A mutation budget rides in GuideP (BudgetP) and adds none.
 // Nor does a confidence threshold (ThreshP in GuideP, guided forms only): workgroup (b, j) is then active iff j < cnt[b], at position
@@ -2713,7 +2722,8 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __re
                                                      const float* __restrict__ q_noise, int q_rows, int q_off,
                                                      RunState* __restrict__ rs, Segs sg, int compact,
                                                      [[maybe_unused]] float* __restrict__ logp, [[maybe_unused]] const int32_t* __restrict__ target,
-                                                     [[maybe_unused]] DrawGuideArg<GUIDED, TRUNC> ga) {
+                                                     [[maybe_unused]] DrawGuideArg<GUIDED, TRUNC> ga,
+                                                     [[maybe_unused]] float* __restrict__ dist) {
     static_assert(GUIDED || !TRUNC, "a truncated session runs the guided form");
     __shared__ float lg[32];
     const int b = blockIdx.x;
@@ -2742,13 +2752,13 @@ __global__ void __launch_bounds__(64 * SS_WAVES) sample_step_k(const float* __re
             if constexpr (TRUNC) { g = ga.g; tr = ga.tr; } else g = ga;
             sample_row<SS_WAVES, MODE, true, TRUNC>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg,
                                                     MODE == DRAW_SAMPLE ? nullptr : logp + bt, MODE == DRAW_SCORE ? target[bt] : 0,
-                                                    g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr,
+                                                    MODE != DRAW_SAMPLE && dist ? dist + bt * 22 : nullptr, g.allow + bt, g.bias ? g.bias + bt * 22 : nullptr, g.temperature, tr,
                                                     budget_at(g.bud, b, sg.L, slot), g.bud.origin ? g.bud.n + b : nullptr);
         } else if constexpr (MODE == DRAW_SAMPLE)
             sample_row<SS_WAVES>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg);
         else
             sample_row<SS_WAVES, MODE>(x, D, w, tokens, b, slot, t, q_noise, q_rows, q_off, rs, sg.L, lg, logp + bt,
-                                       MODE == DRAW_SCORE ? target[bt] : 0);
+                                       MODE == DRAW_SCORE ? target[bt] : 0, dist ? dist + bt * 22 : nullptr);
     } else {
         __syncthreads();                                 // (sample_row has one: every wave has read the step before thread 0 goes on)
     }

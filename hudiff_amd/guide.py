@@ -243,6 +243,30 @@ def guided_log_probs(logits22, allow, bias=None, temperature=1.0, truncation=Non
         return (g - mx) - np.log(np.exp(g - mx).sum(axis=-1, keepdims=True))
 
 
+def dist_entropy(dist):
+    """Entropy in nats, float64 [...], of a distribution record ``dist`` [..., 22] (log-probabilities, -inf = removed; the device's
+    record, model.sample_dist, or ``guided_log_probs``): -sum_j p_j log p_j over the finite entries."""
+    lp = np.asarray(dist, np.float64)
+    if lp.shape[-1] != N_DRAW:
+        raise ValueError(f"dist must end in {N_DRAW} tokens, got {lp.shape}")
+    fin = np.isfinite(lp)
+    lp = np.where(fin, lp, 0.0)
+    return -np.where(fin, np.exp(lp) * lp, 0.0).sum(axis=-1)
+
+
+def dist_log_odds(dist, wt):
+    """Log-odds of every token against the wild type: ``dist - dist[..., wt]``, float64 [..., 22]; ``wt`` int [...] (the residue that
+    is there).  A removed token gives -inf; where the wild type itself is removed every finite entry gives +inf (and -inf - -inf is nan)."""
+    lp = np.asarray(dist, np.float64)
+    if lp.shape[-1] != N_DRAW:
+        raise ValueError(f"dist must end in {N_DRAW} tokens, got {lp.shape}")
+    w = np.asarray(wt, np.int64)
+    if w.shape != lp.shape[:-1] or (w < 0).any() or (w >= N_DRAW).any():
+        raise ValueError(f"wt must be {lp.shape[:-1]} with values in [0, {N_DRAW}), got {w.shape}")
+    with np.errstate(invalid="ignore"):
+        return lp - np.take_along_axis(lp, w[..., None], axis=-1)
+
+
 def confidence_keys(logits, allow=None, bias=None, temperature=1.0, truncation=None):
     """The key of slot_policy="confident" (include/hudiff_hip.h "slot policy") in numpy float64: logits [..., >= 22] (the first 22
     tokens are the draw's), allow [...] uint32 bits or None (everything allowed), bias [..., 22] or None -> log c [...], with

@@ -221,11 +221,11 @@ class _Denoiser:
         return tok, reg, chn, B, was_torch
 
     @staticmethod
-    def _flags(dropout, graph=True, prune=True, lanes=2, record=False):
+    def _flags(dropout, graph=True, prune=True, lanes=2, record=False, dist=False):
         f = {"faithful": L.HD_DROPOUT_FAITHFUL, "off": L.HD_DROPOUT_OFF, "inject": L.HD_DROPOUT_INJECT}[dropout]
         # graph: True = one hipGraph per step replayed T times, "loop" = the whole T-step loop as one hipGraph, False = eager
         return (f | (0 if graph else L.HD_NO_GRAPH) | (L.HD_LOOP_GRAPH if graph == "loop" else 0) | (0 if prune else L.HD_NO_PRUNE)
-                | (0 if lanes == 2 else L.HD_ONE_LANE) | (L.HD_RECORD_LOGP if record else 0))
+                | (0 if lanes == 2 else L.HD_ONE_LANE) | (L.HD_RECORD_LOGP if record else 0) | (L.HD_RECORD_DIST if dist else 0))
 
     def forward(self, H_L_seq, H_L_region_type, H_L_chn_type=None, *, dropout="faithful", seed=0, row0=0,
                 step=0, enc_masks=None, conv_masks=None):
@@ -412,7 +412,7 @@ class _Denoiser:
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1,
-               slot_policy="given", truncation=None, budget=None, confidence=None):
+               slot_policy="given", truncation=None, budget=None, confidence=None, record_dist=False):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
@@ -440,7 +440,11 @@ class _Denoiser:
 
         ``return_logp``: the session records (HD_RECORD_LOGP) and the call returns ``(tokens, logp)``, logp float32 [B, Tmax] = the
         log-probability of the token row b drew at step t under the distribution it was drawn from; 0 where t >= T[b].  The tokens
-        are the same with and without it."""
+        are the same with and without it.
+
+        ``record_dist``: the session keeps the whole 22-token distribution of every draw (HD_RECORD_DIST, include/hudiff_hip.h
+        "distribution record") and records logp too; ``sample_dist()`` / ``sample_logp()`` afterwards return them.  The tokens are the
+        same with and without it."""
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
@@ -448,7 +452,7 @@ class _Denoiser:
         self._session_B, self._session_Tmax = B, Tmax
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
-                                    self._flags(dropout, graph, prune, lanes, bool(return_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
+                                    self._flags(dropout, graph, prune, lanes, bool(return_logp), bool(record_dist)), int(seed), int(row0), L.ptr(q, C.c_float),
                                     L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8)))
         self._warn_on_guard()
         logp = self.sample_logp(B, Tmax) if return_logp else None
@@ -465,6 +469,16 @@ class _Denoiser:
         logp = np.zeros((B, Tmax), dtype=np.float32)
         L.check(self._lib.hd_sample_logp(self._h, L.ptr(logp, C.c_float)))
         return logp
+
+    def sample_dist(self, B=None, Tmax=None):
+        """hd_sample_dist: dist float32 [B, Tmax, 22] of the open session, or of the last one that kept the record (``record_dist``):
+        the log-probability of every token at every position a forward drew or scored, -inf for a token the guide, the budget or the
+        cut removed, 0 where t >= T[b]; ``dist[b, t, token written] == logp[b, t]`` bit for bit."""
+        B = self._session_B if B is None else B
+        Tmax = self._session_Tmax if Tmax is None else Tmax
+        dist = np.zeros((B, Tmax, 22), dtype=np.float32)
+        L.check(self._lib.hd_sample_dist(self._h, L.ptr(dist, C.c_float)))
+        return dist
 
     # -- beam search -------------------------------------------------------------------------------
     def set_beam(self, width):
@@ -555,7 +569,7 @@ class _Denoiser:
 
     # -- likelihood of given sequences -------------------------------------------------------------
     def _score_seq(self, tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide=None, slots_per_step=1, slot_policy="given",
-                   truncation=None, budget=None, confidence=None):
+                   truncation=None, budget=None, confidence=None, want_dist=False):
         logp = np.zeros((B, Tmax), dtype=np.float32)
         self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         self._session_B, self._session_Tmax = B, Tmax
@@ -563,11 +577,11 @@ class _Denoiser:
                                    L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax, flags, int(seed), int(row0),
                                    L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8), L.ptr(logp, C.c_float)))
         self._warn_on_guard()
-        return logp
+        return (logp, self.sample_dist(B, Tmax)) if want_dist else logp
 
     def score(self, tokens, region, chain, order, T, *, dropout="off", parallel=None, device_batch=256, seed=0, row0=0,
               enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given",
-              truncation=None, budget=None, confidence=None):
+              truncation=None, budget=None, confidence=None, record_dist=False, return_dist=False):
         """Log-probability of every given token along a visiting order: logp float32 [B, Tmax],
         logp[b, t] = log p(tokens[b, order[b, t]] | tokens[b] with order[b, t:T[b]] masked); 0 where t >= T[b].  Its sum over t is a
         one-order estimate of the order-agnostic log-likelihood of the scored slots.  ``tokens`` are complete sequences.
@@ -598,8 +612,16 @@ class _Denoiser:
 
         ``budget``: the values are log-probabilities under the budgeted sampler (hudiff_amd.guide.Budget): at a position where the row
         has spent its budget the origin scores 0 and any other token -inf (no error).  Whether a position is exhausted depends on the
-        steps before it, so there is no step-parallel form either."""
+        steps before it, so there is no step-parallel form either.
+
+        ``return_dist``: the sessions keep the distribution record (HD_RECORD_DIST) and the call returns ``(logp, dist)``, dist float32
+        [B, Tmax, 22] = the log-probability of EVERY token at the position logp[b, t] belongs to, under the same distribution (-inf for
+        a token the guide, the budget or the cut removed; 0 where t >= T[b]); ``dist[b, t, target] == logp[b, t]`` bit for bit.
+        Step-parallel: the expanded rows' records fold back by ``Expanded.fold_dist``.  ``record_dist`` alone keeps the record of a
+        sequential call for ``sample_dist()`` without returning it."""
         K = int(slots_per_step)
+        want_dist = bool(return_dist)
+        rec_dist = want_dist or bool(record_dist)
         confident = self._policy_id(slot_policy) != L.HD_SLOTS_GIVEN
         if budget is not None:
             if parallel:
@@ -621,10 +643,13 @@ class _Denoiser:
                              "which an expanded row does not carry; use parallel=False")
         tok, reg, chn, order, T, B, Tmax, _, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, None, enc_masks, conv_masks)
-        flags = self._flags(dropout, graph, prune, lanes)
+        flags = self._flags(dropout, graph, prune, lanes, dist=rec_dist)
+        dist = None
         if not parallel:
             logp = self._score_seq(tok, reg, chn, order, T, B, Tmax, flags, seed, row0, em, cm, guide, K, slot_policy, truncation, budget,
-                                   confidence)
+                                   confidence, want_dist)
+            if want_dist:
+                logp, dist = logp
         else:
             from . import scoring
             x = scoring.expand_steps(tok, reg, chn, order, T, slots_per_step=K)      # (K outside [1, 64]: ValueError)
@@ -637,40 +662,49 @@ class _Denoiser:
             rr = np.broadcast_to(np.arange(n)[:, None], (n, K))[live]
             x.tokens[rr, x.order[live]] = tok[x.rows[rr], x.order[live]]
             flat = np.zeros((n, K), dtype=np.float32)
+            flat_dist = np.zeros((n, K, 22), dtype=np.float32) if want_dist else None
             for s in range(0, n, int(device_batch)):
                 e = min(n, s + int(device_batch))
                 ch = None if x.chain is None else np.ascontiguousarray(np.concatenate([x.chain[s:e], x.chain[n + s:n + e]]))
-                flat[s:e] = self._score_seq(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
-                                            np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, K, flags,
-                                            seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]), K,
-                                            truncation=truncation)
+                got = self._score_seq(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
+                                      np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), e - s, K, flags,
+                                      seed, 0, None, None, None if guide is None else guide.take(x.rows[s:e]), K,
+                                      truncation=truncation, want_dist=want_dist)
+                if want_dist:
+                    flat[s:e], flat_dist[s:e] = got
+                else:
+                    flat[s:e] = got
             logp = x.fold(flat, Tmax)
+            if want_dist:
+                dist = x.fold_dist(flat_dist, Tmax)
         if was_torch:
             import torch
-            return torch.from_numpy(logp)
-        return logp
+            logp = torch.from_numpy(logp)
+            dist = None if dist is None else torch.from_numpy(dist)
+        return (logp, dist) if want_dist else logp
 
     def score_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, dropout="off", enc_masks=None, conv_masks=None,
-                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None, budget=None, confidence=None):
+                    graph=True, prune=True, lanes=2, guide=None, slots_per_step=1, slot_policy="given", truncation=None, budget=None, confidence=None,
+                    record_dist=False):
         """hd_score_begin: a teacher-forced recording session; sample_run / sample_restart / sync / sample_end / sample_tokens /
-        last_run_ms / sample_logp work on it as on a sampling session."""
+        last_run_ms / sample_logp work on it as on a sampling session, and sample_dist with ``record_dist``."""
         tok, reg, chn, order, T, B, Tmax, _, em, cm, _ = self._sample_args(tokens, region, chain, order, T, None, enc_masks, conv_masks)
         self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         L.check(self._lib.hd_score_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                          L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
-                                         self._flags(dropout, graph, prune, lanes), int(seed), int(row0),
+                                         self._flags(dropout, graph, prune, lanes, dist=bool(record_dist)), int(seed), int(row0),
                                          L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8)))
         self._session_B, self._session_Tmax = B, Tmax
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                      enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1,
-                     slot_policy="given", truncation=None, budget=None, confidence=None):
+                     slot_policy="given", truncation=None, budget=None, confidence=None, record_dist=False):
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
-                                          self._flags(dropout, graph, prune, lanes, bool(record_logp)), int(seed), int(row0), L.ptr(q, C.c_float),
+                                          self._flags(dropout, graph, prune, lanes, bool(record_logp), bool(record_dist)), int(seed), int(row0), L.ptr(q, C.c_float),
                                           L.ptr(em, C.c_uint8), L.ptr(cm, C.c_uint8)))
         self._session_B, self._session_Tmax = B, Tmax
 

@@ -46,6 +46,17 @@ class Expanded:
         out[np.broadcast_to(self.rows[:, None], (N, K))[live], (self.steps[:, None] + j)[live]] = flat[live]
         return out
 
+    def fold_dist(self, flat, Tmax: int) -> np.ndarray:
+        """The distribution records of the rows, [N, K, 22] (a session's ``sample_dist``), -> [B, Tmax, 22] float32, 0 where
+        t >= T[b]: as ``fold``, 22 values per position."""
+        N, K = self.rows.shape[0], self.slots_per_step
+        flat = np.asarray(flat, np.float32).reshape(N, K, 22)
+        out = np.zeros((self.B, Tmax, 22), np.float32)
+        j = np.arange(K)[None, :]
+        live = j < np.asarray(self.T)[:, None]
+        out[np.broadcast_to(self.rows[:, None], (N, K))[live], (self.steps[:, None] + j)[live]] = flat[live]
+        return out
+
 
 def expand_steps(tokens, region, chain, order, T, slots_per_step: int = 1) -> Expanded:
     """Every (b, t < T[b]) becomes one row: the complete tokens of row b with ``order[b, t:T[b]]`` masked, row b's region and
@@ -209,3 +220,106 @@ def score_jobs(model, jobs: Sequence, orders: int = 1, seed: int = 0, *, dropout
         std = total.std(axis=1)
     return {"total": total, "mean": mean, "std": std, "per_residue": np.where(T > 0, mean / np.maximum(T, 1), 0.0),
             "T": T, "logp": logp, "order": all_order}
+
+
+SCAN_GROUP = 64                          # slots one row of a context="masked" scan scores: the largest block size (hd_set_slots_per_step)
+SCAN_CONTEXTS = ("given", "masked")
+
+
+def expand_scan(tokens, region, chain, loc, T, context: str = "given") -> Expanded:
+    """The rows of a mutational scan of the slots ``loc[b, :T[b]]`` of complete sequences ``tokens`` [B, L].
+
+    ``context="given"`` (the pseudo-likelihood form): every (b, s in loc[b]) becomes one row -- the complete row with slot s alone
+    masked, order ``[s]``, T = 1.  Rows are b-major, in the order of ``loc``.
+
+    ``context="masked"`` (the distribution the sampler meets at its first step): every job becomes ceil(T / 64) rows, each with ALL of
+    ``loc[b]`` masked and a group of at most 64 of the slots as its order (0-padded to 64), to be scored in sessions of block size 64
+    with Tmax = 64.  A row holds one group only, so no group sees another's targets."""
+    if context not in SCAN_CONTEXTS:
+        raise ValueError(f"context must be one of {SCAN_CONTEXTS}, got {context!r}")
+    tokens = np.asarray(tokens, np.int32)
+    region = np.asarray(region, np.int32)
+    T = np.asarray(T, np.int64).reshape(-1)
+    B, L = tokens.shape
+    loc = np.asarray(loc, np.int32)
+    loc = loc.reshape(B, loc.shape[1] if loc.ndim == 2 else (loc.size // B if B else 0))
+    if T.shape[0] != B or (T < 0).any() or (T > loc.shape[1]).any():
+        raise ValueError(f"T must be [{B}] with 0 <= T[b] <= {loc.shape[1]}")
+    K = 1 if context == "given" else SCAN_GROUP
+    rows = np.repeat(np.arange(B), (T + K - 1) // K)
+    steps = np.concatenate([np.arange(0, t, K) for t in T] + [np.zeros(0, np.int64)]).astype(np.int64)
+    N = rows.shape[0]
+    tok = tokens[rows].copy()
+    grp = np.zeros((N, K), np.int32)
+    Tg = np.zeros(N, np.int32)
+    for i in range(N):
+        b, t0, n = int(rows[i]), int(steps[i]), int(T[rows[i]])
+        Tg[i] = min(K, n - t0)
+        grp[i, :Tg[i]] = loc[b, t0:t0 + Tg[i]]
+        tok[i, grp[i, :Tg[i]] if K == 1 else loc[b, :n]] = MASK_TOKEN
+    ch = None
+    if chain is not None:
+        chain = np.asarray(chain, np.int32).reshape(-1)
+        if chain.shape[0] != 2 * B:
+            raise ValueError(f"chain must be [{2 * B}] (heavy ids, then light ids)")
+        ch = np.concatenate([chain[:B][rows], chain[B:][rows]]).astype(np.int32)
+    return Expanded(tokens=tok, region=region[rows].copy(), chain=ch, order=grp, T=Tg, rows=rows, steps=steps, B=B, slots_per_step=K)
+
+
+def scan_jobs(model, jobs: Sequence, *, context: str = "given", device_batch: int = 256, all_ranks: bool = False,
+              temperature: float = 1.0, truncation=None):
+    """Mutational scan: the model's whole 22-token distribution at every slot of every job's ``loc``, read from the device's
+    distribution record (include/hudiff_hip.h "distribution record") -- one forward per row of ``expand_scan``, not one per token.
+
+    ``Job.tokens`` are COMPLETE sequences, as for ``score_jobs``; the jobs' ``guide`` fields, ``temperature`` and ``truncation`` shape
+    the distribution as they shape a draw.  ``context``: "given" = every other residue is known (pseudo-likelihood), "masked" = all of
+    ``loc`` is masked.  Dropout is off; the expanded rows carry no (row, step) key, as in step-parallel scoring.  Rows shard over ranks
+    and are gathered once.  Returns on rank 0 (every rank when single-process or ``all_ranks``; None elsewhere) a dict:
+      dist [J, Tmax, 22] float32  log p of every token (guide.LETTERS order) at position t of ``loc``; -inf = removed; 0 where t >= T
+      slot [J, Tmax] int32        the slot of position t         wt [J, Tmax] int32      the residue the sequence has there
+      logp_wt [J, Tmax] float32   dist at the wild type          entropy [J, Tmax] float64 (nats, guide.dist_entropy)
+      T [J]                       scanned slots                  pseudo_ll [J] float64   sum_t logp_wt."""
+    from .guide import Guide, dist_entropy
+    J = len(jobs)
+    is_ab = model.kind == "ab"
+    Lm = model.max_len
+    Tmax = max([len(j.loc) for j in jobs] + [1])
+    T = np.array([len(j.loc) for j in jobs], np.int64)
+    slot = np.zeros((J, Tmax), np.int32)
+    for j, job in enumerate(jobs):
+        slot[j, :T[j]] = np.asarray(job.loc, np.int32)
+    tok = np.stack([np.asarray(j.tokens) for j in jobs]).astype(np.int32) if J else np.zeros((0, Lm), np.int32)
+    reg = np.stack([j.region for j in jobs]).astype(np.int32) if J else np.zeros((0, Lm), np.int32)
+    chain = np.array([j.chain[0] for j in jobs] + [j.chain[1] for j in jobs], np.int32) if is_ab else None
+    x = expand_scan(tok, reg, chain, slot, T, context)
+    N, K = x.rows.shape[0], x.slots_per_step
+    # a scoring session takes its targets from the tokens it is given (and masks the scored slots itself): the wild type goes back
+    live = np.arange(K)[None, :] < x.T[:, None]
+    rr = np.broadcast_to(np.arange(N)[:, None], (N, K))[live]
+    x.tokens[rr, x.order[live]] = tok[x.rows[rr], x.order[live]]
+    guided = float(temperature) != 1.0 or any(j.guide is not None for j in jobs)
+    more = {}
+    if truncation is not None and not truncation.neutral:
+        more["truncation"] = truncation
+    rank, world, _ = D.env_rank_world()
+    lo, hi = D.shard_bounds(N, rank, world)
+    flat = np.zeros((hi - lo, K, 22), np.float32)
+    for s in range(lo, hi, int(device_batch)):
+        e = min(hi, s + int(device_batch))
+        ch = None if x.chain is None else np.ascontiguousarray(np.concatenate([x.chain[s:e], x.chain[N + s:N + e]]))
+        if guided:
+            more["guide"] = Guide.stack([jobs[b].guide for b in x.rows[s:e]], Lm, temperature)
+        _, flat[s - lo:e - lo] = model.score(np.ascontiguousarray(x.tokens[s:e]), np.ascontiguousarray(x.region[s:e]), ch,
+                                             np.ascontiguousarray(x.order[s:e]), np.ascontiguousarray(x.T[s:e]), dropout="off",
+                                             parallel=False, slots_per_step=K, return_dist=True, **more)
+    # one gather, as for the tokens: the float32 bits travel as int32
+    got = D.gather_rows(flat.reshape(hi - lo, K * 22).view(np.int32), N, K * 22, all_ranks)
+    if got is None:
+        return None
+    dist = x.fold_dist(np.ascontiguousarray(got, dtype=np.int32).view(np.float32).reshape(N, K, 22), Tmax)
+    wt = np.take_along_axis(tok, slot, axis=1).astype(np.int32) if J else np.zeros((0, Tmax), np.int32)
+    valid = np.arange(Tmax)[None, :] < T[:, None]
+    wt = np.where(valid, wt, 0).astype(np.int32)
+    logp_wt = np.where(valid, np.take_along_axis(dist, wt[..., None].astype(np.int64), axis=2)[..., 0], np.float32(0)).astype(np.float32)
+    return {"dist": dist, "slot": slot, "wt": wt, "logp_wt": logp_wt, "entropy": np.where(valid, dist_entropy(dist), 0.0), "T": T,
+            "pseudo_ll": logp_wt.astype(np.float64).sum(axis=1)}

@@ -62,8 +62,9 @@ extern "C" {
                                  the struct HdGuide; block decoding added hd_set_slots_per_step; the slot policy added hd_set_slot_policy and
                                  hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation; beam search added hd_set_beam and
                                  hd_beam_state; the mutation budget added hd_set_budget, hd_mutation_count and the struct HdBudget; the confidence
-                                 threshold added hd_set_confidence, hd_sample_run_to_end, hd_sample_progress, hd_sample_forwards and hd_sample_keys -- entry
-                                 points only, so the version is unchanged */
+                                 threshold added hd_set_confidence, hd_sample_run_to_end, hd_sample_progress, hd_sample_forwards and hd_sample_keys; the
+                                 distribution record added hd_sample_dist and the flag HD_RECORD_DIST -- entry points only, so the version is
+                                 unchanged */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -93,8 +94,11 @@ enum {
     HD_LOOP_GRAPH       = 32u, /* hd_sample / hd_sample_run: the whole T-step loop of a lane is ONE hipGraph (a chain
                                   of T child-graph nodes of the captured step) launched once, instead of T replays
                                   of the step graph (same results; measured 2.4 % slower on MI355X) */
-    HD_RECORD_LOGP      = 64u  /* hd_sample / hd_sample_begin: the session records the log-probability of every token it writes
+    HD_RECORD_LOGP      = 64u, /* hd_sample / hd_sample_begin: the session records the log-probability of every token it writes
                                   (hd_sample_logp); the drawn tokens are the same with and without the flag             */
+    HD_RECORD_DIST      = 128u /* hd_sample / hd_sample_begin / hd_score_begin / hd_score: the session keeps the whole 22-token
+                                  distribution of every draw ("distribution record", hd_sample_dist); a sampling session with it
+                                  records logp too; tokens, logp and order are the same with and without the flag        */
 };
 
 /* Hyper-parameters: the `model:` section of configs/antibody_train.yml:3-24 / heavy_train.yml:3-21,
@@ -507,6 +511,35 @@ HdStatus hd_sample_run_to_end(HdModel* m, int32_t chunk, int32_t* forwards /* ma
 HdStatus hd_sample_progress(HdModel* m, int32_t* filled /* [B] */);
 HdStatus hd_sample_forwards(HdModel* m, int32_t* fwd /* [B, Tmax] */);
 HdStatus hd_sample_keys(HdModel* m, float* conf /* [B, Tmax] */);
+
+/* ---- distribution record --------------------------------------------------------------------------
+ * A session begun with the flag HD_RECORD_DIST (hd_sample, hd_sample_begin, hd_score_begin, hd_score) keeps dist [B, Tmax, 22] float32:
+ * the distribution every draw was taken from, or every target was scored under.  A sampling session with the flag records logp too, as
+ * under HD_RECORD_LOGP.
+ *
+ * For row b at order position t < T[b] that a forward drew or scored, with g_j, mx = max g, esum and the allowed / kept sets as the draw
+ * stage forms them -- after the guide ("guided sampling"), the temperature, the forced set of an exhausted budget ("mutation budget") and
+ * the renormalisation of the cut ("truncated sampling"):
+ *     dist[b, t, j] = (g_j - mx) - logf(esum)     if token j is allowed and kept
+ *                   = -inf                         otherwise
+ * the same three fp32 operations in the same order as logp[b, t].  Consequences:
+ *   - dist[b, t, token written] == logp[b, t] bit for bit wherever that logp is finite;
+ *   - where a scoring session records -inf (a target the cut removed, a mutation an exhausted budget no longer pays for) the target's
+ *     entry is -inf too;
+ *   - an exhausted budgeted draw has +0.0f at its origin and -inf at the 21 other tokens;
+ *   - temperature 0 records the temperature-1 distribution, the one its logp is under;
+ *   - entries with t >= T[b], or of positions not yet run, are 0; a row that raised the numeric flag has unspecified entries.
+ * The index is the (b, t) of logp: with block decoding, the confident policy and the threshold, position t holds the distribution of the
+ * entry the selection put there.  The stores happen inside the draw launch (lanes 0..21 of one wave, 88 contiguous bytes): a session
+ * with the flag launches what it launches without it, and tokens, logp and order are the same bits.
+ *
+ * hd_sample_dist copies dist [B, Tmax, 22] out, rows in whole-batch order whatever the lane split.  Legal exactly where hd_sample_logp
+ * is: inside an open session (it synchronises; HD_ERR_STATE after a guard has fired -- hd_sample_end repeats the sample and the values
+ * read back then come from the repeat) and after hd_sample / hd_sample_end / hd_score until the next begin or hd_forward.  A session
+ * without the flag -> HD_ERR_STATE.  hd_sample_restart zeroes the record.
+ *
+ * The flag with a beam width pending (hd_set_beam) -> HD_ERR_UNSUPPORTED: a beam session has its candidate table (hd_beam_state). */
+HdStatus hd_sample_dist(HdModel* m, float* dist /* [B, Tmax, 22] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
