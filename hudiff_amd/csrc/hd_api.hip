@@ -11,6 +11,7 @@
 #include "hd_attn_fused.hip.h"
 #include "hd_chain.hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -315,6 +316,7 @@ struct HdModel {
     bool s_dirty = false;                            // a guard fired in the steps run since the last begin / restart: their tokens are invalid
     int last_steps = 0; bool timed = false;
     int debug_stop_after = 0;     // 0 = run everything (hd_debug_stop_after)
+    int x3_refused = 0;           // weight guard (X3Packer::add) refused a split image: bit 0 ByteNet stacks, bit 1 attention blocks run the fp32 GEMMs
     int64_t tally[HD_DBG_COUNT] = {};   // hd_debug_launch_tally: launches issued per kernel choice (host side; tests only)
     bool debug_lnsync_fail = false;   // hd_debug_fail_next_lnsync: ln_sync meetings of the next call give up after one poll
 };
@@ -592,7 +594,13 @@ static void fold_layernorm(std::vector<float>& w, std::vector<float>& b, const s
 // w: nseg matrices [Ktot, N] (row-major, back to back).  Output per segment: tiles [N/128][Ktot/32] of hi[128 n][32 k] then
 // lo[128][32] fp16, values scaled by 2^shift with shift chosen so that the largest |w| lands in [2^13, 2^14): the lo parts
 // (2^-11 of the value) then stay normal fp16 numbers for everything within 2^-12 of the largest weight.
-struct X3Off { size_t off = 0; long seg_stride = 0; float acc_scale = 1.f; long ntile_stride = 0; bool ok = false; };
+// Weight dynamic range (include/hudiff_hip.h "weight guard"): one scale serves the whole matrix, so an entry far below the largest one
+// has a subnormal lo -- or a subnormal hi -- and keeps fewer than the route's 22 significand bits.  add() therefore measures the image it
+// wrote: every entry must be held to 2^-22 of itself or, where it is smaller than that, of the median |w| of the matrix's non-zero entries (an ordinary entry:
+// the median ignores the few outliers that set the scale).  An image that is not is refused (ok = false) and hd_finalize keeps the
+// blocks of its family on the fp32 kernels.  A property of the matrix alone; freshly initialised and trained-like matrices (largest
+// entry within 2^16 of the median) always pass.
+struct X3Off { size_t off = 0; long seg_stride = 0; float acc_scale = 1.f; long ntile_stride = 0; bool ok = false; bool refused = false; };      // refused: by the weight guard
 struct X3Packer {
     std::vector<uint16_t> buf;
     static uint16_t h16(float x) { _Float16 h = (_Float16)x; uint16_t u; memcpy(&u, &h, 2); return u; }
@@ -608,6 +616,18 @@ struct X3Packer {
         if (mx > 0.f) frexpf(mx, &e);                   // mx = f * 2^e, f in [0.5, 1)
         const int shift = 14 - e;                       // mx * 2^shift in [2^13, 2^14)
         const float sc = ldexpf(1.f, shift);
+        double med = 0.0;                               // median |w|, scaled like the image
+        if (!w.empty()) {
+            std::vector<float> a;                       // the non-zero entries: a pruned matrix is judged by the entries it has
+            a.reserve(w.size());
+            for (float v : w) if (v != 0.f) a.push_back(fabsf(v));
+            if (!a.empty()) {
+                std::nth_element(a.begin(), a.begin() + a.size() / 2, a.end());
+                med = (double)a[a.size() / 2] * (double)sc;
+            }
+        }
+        const double rel = ldexp(1.0, -22);
+        bool held = true;
         o.off = (buf.size() + 63) / 64 * 64;
         const int nt = N / X3_BN, kt = Ktot / X3_BK;
         o.seg_stride = (long)nt * kt * X3_TILE_HALFS;
@@ -631,9 +651,12 @@ struct X3Packer {
                             const int pos = n * X3_BK + ((((k >> 3) ^ ((n >> 2) & 3)) << 3) | (k & 7));
                             t[pos] = h16(hi);
                             t[X3_BN * X3_BK + pos] = h16(v - hi);
+                            const double err = fabs((double)v - ((double)hi + (double)f16(v - hi)));
+                            if (err > rel * fmax(fabs((double)v), med)) held = false;
                         }
                 }
         }
+        if (!held) { buf.resize(o.off); X3Off r; r.refused = true; return r; }      // weight guard: the image would not hold the matrix to 22 bits
         o.ok = true;
         return o;
     }
@@ -844,6 +867,14 @@ extern "C" HdStatus hd_finalize(HdModel* m) {
     };
     for (auto& o : enc_off) enc_x.push_back(bnx(o, d, dh));
     for (auto& o : conv_off) conv_x.push_back(bnx(o, D, Dh));
+    // weight guard (X3Packer::add): one refused image takes its whole family -- the ByteNet stacks here, the attention blocks below -- off the
+    // split kernels, the granularity HD_OPT_SPLIT_LAYER_MASK already runs at (blocks of a family hand each other split operands)
+    if (xp_bn) {
+        bool any = false;
+        for (auto* v : {&enc_x, &conv_x})
+            for (auto& x : *v) any = any || x.wc.refused || x.w1.refused || x.w3.refused || x.w3p.refused;
+        if (any) { for (auto* v : {&enc_x, &conv_x}) for (auto& x : *v) x = BnX(); m->x3_refused |= 1; }
+    }
     struct AttOff { AttLayerOff a1, a2; size_t n1_g, n1_b, n2_g, n2_b, wf1, bf1, wf2, bf2; X3Off wf1x, wf2x; };
     std::vector<AttOff> att_off;
     for (int n = 0; n < c.cs_layers; ++n) {
@@ -868,6 +899,11 @@ extern "C" HdStatus hd_finalize(HdModel* m) {
             if (xp_at) o.wf2x = xp_at->add(wf2, 1, Fd, D);
         }
         att_off.push_back(o);
+    }
+    if (xp_at) {
+        bool any = false;
+        for (auto& o : att_off) any = any || o.a1.wqkvx.refused || o.a1.wox.refused || o.a2.wqkvx.refused || o.a2.wox.refused || o.wf1x.refused || o.wf2x.refused;
+        if (any) { for (auto& o : att_off) o.a1.wqkvx = o.a1.wox = o.a2.wqkvx = o.a2.wox = o.wf1x = o.wf2x = X3Off(); m->x3_refused |= 2; }
     }
     // region / position branch
     const int re = c.r_embedding;
@@ -2714,9 +2750,9 @@ extern "C" HdStatus hd_precision_report(HdModel* m, HdPrecisionInfo* out, size_t
     if (!m || !out) return fail(HD_ERR_INVALID, "hd_precision_report: null argument");
     HdPrecisionInfo r{};
     r.precision = m->finalized ? m->precision : m->precision_req;
-    r.split_built = (m->x3 ? 1 : 0) | (m->attn_x3 ? 2 : 0);
+    r.split_built = (m->x3 && !m->x3_refused ? 1 : 0) | (m->attn_x3 ? 2 : 0);
     r.split_in_use = (m->finalized && split_active(m)) ? 1 : 0;
-    r.lnsync_in_use = (m->finalized && m->x3 && !m->x3_suspended && m->lnsync_level > 0) ? 1 : 0;
+    r.lnsync_in_use = (m->finalized && m->x3 && !(m->x3_refused & 1) && !m->x3_suspended && m->lnsync_level > 0) ? 1 : 0;      // (the ByteNet GEMMs of a refused family are fp32 ones)
     r.range_fallbacks = m->range_fallbacks;
     r.lnsync_fallbacks = m->lnsync_fallbacks;
     r.last_call_repeated = m->last_call_repeated ? 1 : 0;
@@ -2738,7 +2774,7 @@ extern "C" HdStatus hd_precision_reset(HdModel* m) {
 
 extern "C" HdStatus hd_precision_info(HdModel* m, int32_t* split_built, int32_t* split_in_use, int64_t* range_fallbacks) {
     if (!m) return fail(HD_ERR_INVALID, "hd_precision_info: null model");
-    if (split_built) *split_built = (m->x3 ? 1 : 0) | (m->attn_x3 ? 2 : 0);
+    if (split_built) *split_built = (m->x3 && !m->x3_refused ? 1 : 0) | (m->attn_x3 ? 2 : 0);
     if (split_in_use) *split_in_use = split_active(m) ? 1 : 0;
     if (range_fallbacks) *range_fallbacks = m->range_fallbacks;
     return HD_OK;

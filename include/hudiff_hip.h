@@ -576,6 +576,15 @@ double hd_flops_per_row_sample_step(const HdConfig* cfg);
  *                 its values; when one is out of range, hd_forward / hd_sample[_end] repeats the whole call on the fp32 kernels (same
  *                 resident inputs, same noise key, same steps) and the handle stays on them (weights whose stream leaves the
  *                 range do so at every step) until hd_precision_reset.  hd_sample_restart and hd_sync notice the flag as well.
+ *   weight guard  a split weight image scales its whole matrix by ONE power of two (largest |w| into [2^13, 2^14)), so entries far
+ *                 below the largest one keep fewer than 22 bits (subnormal lo, then subnormal hi).  hd_finalize builds an image only
+ *                 if every entry's (hi, lo) pair is within 2^-22 of the entry or, where that is larger, of the median |w| of the
+ *                 matrix's NON-ZERO entries (a pruned matrix is judged by the entries it has) -- a property of the matrix alone,
+ *                 true whenever its largest entry is within about 2^16 of that median.  A matrix that fails keeps its whole family
+ *                 (ByteNet stacks / attention blocks) on the fp32 GEMMs; the other family keeps its images.  The report then reads:
+ *                 split_built bit 0 clear (an image was refused, whichever family), lnsync_in_use 0 if the ByteNet family was
+ *                 refused, split_built bit 1 unchanged (the core is built; a refused attention family runs attn_k beside its fp32
+ *                 GEMMs, like split_layer_mask = 1), split_in_use unchanged (nothing was switched off by the range guard).
  *   ln_sync guard the ByteNet GEMMs of the split route normalise their own output rows: the N tiles of an M tile exchange LayerNorm
  *                 partials at a counter (write-through stores, agent-scope loads: correct wherever the blocks run), which presumes
  *                 they are co-resident.  A meeting that times out raises a flag; the call is repeated with separate LayerNorm passes
@@ -584,7 +593,7 @@ enum { HD_PRECISION_DEFAULT = 0, HD_PRECISION_F32_GEMM = 1, HD_PRECISION_F32_ALL
 HdStatus hd_set_precision(HdModel* m, int32_t precision);
 typedef struct HdPrecisionInfo {
     int32_t precision;          /* resolved route of the handle: HD_PRECISION_SPLIT / F32_GEMM / F32_ALL (never DEFAULT after hd_finalize) */
-    int32_t split_built;        /* bit 0: split-precision weight images exist (GEMMs), bit 1: split-precision attention core     */
+    int32_t split_built;        /* bit 0: split-precision weight images exist (GEMMs; none refused by the weight guard), bit 1: split-precision attention core */
     int32_t split_in_use;       /* 1 while eligible launches take the split kernels, 0 after the range guard switched them off   */
     int32_t lnsync_in_use;      /* 1 while the split ByteNet GEMMs normalise their own outputs, 0 = separate ln_apply_k passes   */
     int64_t range_fallbacks;    /* calls repeated on the fp32 kernels by the range guard                                          */
