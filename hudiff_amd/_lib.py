@@ -21,6 +21,7 @@ HD_RECORD_LOGP = 64
 HD_RECORD_DIST = 128
 HD_SLOTS_GIVEN, HD_SLOTS_CONFIDENT = 0, 1
 BEAM_MAX_WIDTH = 64
+REFINE_MAX_ROUNDS, REFINE_MAX_SLOTS = 16, 64
 SLOT_POLICIES = {"given": HD_SLOTS_GIVEN, "confident": HD_SLOTS_CONFIDENT}
 HD_PRECISION_DEFAULT, HD_PRECISION_F32_GEMM, HD_PRECISION_F32_ALL, HD_PRECISION_SPLIT = 0, 1, 2, 3
 PRECISIONS = {"default": HD_PRECISION_DEFAULT, "split": HD_PRECISION_SPLIT, "f32_gemm": HD_PRECISION_F32_GEMM, "f32_all": HD_PRECISION_F32_ALL}
@@ -40,6 +41,7 @@ EXPORTS = [
     "hd_set_budget", "hd_mutation_count",
     "hd_set_confidence", "hd_sample_run_to_end", "hd_sample_progress", "hd_sample_forwards", "hd_sample_keys",
     "hd_sample_dist",
+    "hd_set_refine", "hd_refine_state",
 ]
 
 # tuning options (include/hudiff_hip.h, HdOption): name -> id; the names are the enum's, lower case without the HD_OPT_ prefix
@@ -161,6 +163,8 @@ def load():
     lib.hd_sample_forwards.argtypes = [vp, i32p]
     lib.hd_sample_keys.argtypes = [vp, f32p]
     lib.hd_sample_dist.argtypes = [vp, f32p]
+    lib.hd_set_refine.argtypes = [vp, C.c_int32, C.c_int32, C.c_float]
+    lib.hd_refine_state.argtypes = [vp, i32p, i32p, i32p]
     lib.hd_debug_stop_after.argtypes = [vp, C.c_int32]
     lib.hd_debug_read.argtypes = [vp, C.c_char_p, C.c_int32, f32p, C.c_int64]
     _lib = lib

@@ -150,6 +150,7 @@ def apply_block_args(args, jobs, logger=None, forward_stats=None):
     --confidence run counts its forwards into (log_forward_stats)."""
     k = int(args.slots_per_step)
     more = apply_truncation_args(args, logger)
+    more.update(apply_refine_args(args, logger))
     if getattr(args, "slot_policy", "given") != "given":
         more["slot_policy"] = args.slot_policy
         if logger is not None:
@@ -198,8 +199,65 @@ def max_mutations_arg(v):
     return n
 
 
+def refine_rounds_arg(v):
+    n = int(v)
+    if not 0 <= n <= 16:
+        import argparse
+        raise argparse.ArgumentTypeError(f"{v}: an integer in [0, 16]")
+    return n
+
+
+def refine_slots_arg(v):
+    n = int(v)
+    if not 1 <= n <= 64:
+        import argparse
+        raise argparse.ArgumentTypeError(f"{v}: an integer in [1, 64]")
+    return n
+
+
+def refine_below_arg(v):
+    import argparse
+    try:
+        x = float(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{v}: a finite number <= 0") from None
+    if not (x <= 0.0 and x > float("-inf")):          # (NaN fails both)
+        raise argparse.ArgumentTypeError(f"{v}: a finite number <= 0")
+    return x
+
+
+def add_refine_args(p):
+    """--refine_rounds / --refine_slots / --refine_below of the four samplers (refinement rounds, include/hudiff_hip.h); without
+    --refine_rounds the run is today's."""
+    p.add_argument("--refine_rounds", type=refine_rounds_arg, default=0,
+                   help="refinement rounds: after a row has drawn all its positions, its least likely ones are masked again and redrawn "
+                        "with everything else as context, this many times, in [0, 16]; 0 (default) = none")
+    p.add_argument("--refine_slots", type=refine_slots_arg, default=None, metavar="R",
+                   help="positions redrawn per round, in [1, 64] (default 8); needs --refine_rounds")
+    p.add_argument("--refine_below", type=refine_below_arg, default=None, metavar="LOGP",
+                   help="only positions whose recorded log-probability is below LOGP (finite, <= 0; default 0: every position drawn "
+                        "with probability < 1) are redrawn; needs --refine_rounds")
+    return p
+
+
+def apply_refine_args(args, logger=None):
+    """-> {"refine": dict(rounds=, slots=, below=)} for sample_jobs[_with_retry], or {} without --refine_rounds (the calls are then
+    exactly today's)."""
+    n = int(getattr(args, "refine_rounds", 0) or 0)
+    if n == 0:
+        return {}
+    slots = getattr(args, "refine_slots", None)
+    below = getattr(args, "refine_below", None)
+    refine = dict(rounds=n, slots=8 if slots is None else int(slots), below=0.0 if below is None else float(below))
+    if logger is not None:
+        logger.info("Refinement: {rounds} round(s) of {slots} slot(s), log-probability below {below}".format(**refine))
+    return {"refine": refine}
+
+
 def add_budget_args(p):
-    """--max_mutations of the four samplers (mutation budget, include/hudiff_hip.h); without it the run is today's."""
+    """--max_mutations of the four samplers (mutation budget, include/hudiff_hip.h); without it the run is today's.  The refinement
+    flags (add_refine_args) ride along: the same four commands take them."""
+    add_refine_args(p)
     p.add_argument("--max_mutations", type=max_mutations_arg, default=None,
                    help="mutation budget: every written sequence differs from its input in at most N of the sampled positions -- a row "
                         "that has changed N of them keeps the input's residue from then on; composes with --beam (the W most likely "
@@ -224,6 +282,16 @@ def apply_budget_args(args, jobs, logger=None):
 def parse_with_beam(p, argv):
     """parse_args, and the combinations --beam and --max_mutations do not take are argparse errors."""
     args = check_confidence_args(p, p.parse_args(argv))
+    if not getattr(args, "refine_rounds", 0):
+        if getattr(args, "refine_slots", None) is not None or getattr(args, "refine_below", None) is not None:
+            p.error("--refine_slots / --refine_below describe refinement rounds: they need --refine_rounds")
+    else:
+        if args.beam:
+            p.error("--refine_rounds redraws sampled positions: not together with --beam")
+        if getattr(args, "confidence", None) is not None:
+            p.error("--refine_rounds opens its rounds by the step: not together with --confidence")
+        if getattr(args, "max_mutations", None) is not None:
+            p.error("--refine_rounds would count a redrawn position twice: not together with --max_mutations")
     if getattr(args, "max_mutations", None) is not None:
         if int(args.slots_per_step) > 1:
             p.error("--max_mutations counts one slot per forward: not together with --slots_per_step > 1")
@@ -351,18 +419,20 @@ def load_numbered(path):
     return rows
 
 
-def write_logp_csv(path, rows, sweep=False):
+def write_logp_csv(path, rows, sweep=False, redrawn=False):
     """Sidecar of a sampling run (``--logp_fpath``): one line per SAMPLED row, 'name,pass,replica,T,logp,chosen' (with ``sweep``:
     'name,sweep,pass,replica,T,logp,chosen').  T = slots the row sampled, logp = their total log-probability under the distributions
-    they were drawn from, chosen = 1 when the row was written to sample_humanization_result.csv."""
-    width = 7 if sweep else 6
+    they were drawn from, chosen = 1 when the row was written to sample_humanization_result.csv.  ``redrawn`` (a run with
+    --refine_rounds): a last column 'redrawn', the number of positions the row redrew; logp is then the total over the LIVE positions
+    -- every position under the distribution its final residue was drawn from."""
+    width = (7 if sweep else 6) + (1 if redrawn else 0)
     with open(path, "w", encoding="UTF-8") as f:
-        f.write("name,sweep,pass,replica,T,logp,chosen\n" if sweep else "name,pass,replica,T,logp,chosen\n")
+        f.write(("name,sweep,pass,replica,T,logp,chosen" if sweep else "name,pass,replica,T,logp,chosen") + (",redrawn\n" if redrawn else "\n"))
         for row in rows:
             if len(row) != width:
                 raise ValueError(f"a row of the log-probability sidecar has {width} fields, got {row!r}")
-            *head, T, logp, chosen = row
-            f.write(",".join(str(x) for x in head) + f",{int(T)},{float(logp):.6f},{int(chosen)}\n")
+            *head, T, logp, chosen = row[:-1] if redrawn else row
+            f.write(",".join(str(x) for x in head) + f",{int(T)},{float(logp):.6f},{int(chosen)}" + (f",{int(row[-1])}\n" if redrawn else "\n"))
     return path
 
 

@@ -158,7 +158,9 @@ def main(argv=None):
     if rank != 0:
         return None
     if records is not None:
-        write_logp_csv(args.logp_fpath, [(jobs[j].name, sweep, 0, r, T, lp, ch) for j, sweep, r, T, lp, ch in sorted(records)], sweep=True)
+        # (--refine_rounds: a record carries a seventh field, the positions the row redrew)
+        write_logp_csv(args.logp_fpath, [(jobs[rec[0]].name, rec[1], 0) + tuple(rec[2:]) for rec in sorted(records)], sweep=True,
+                       redrawn=bool(args.refine_rounds))
     save_fpath = os.path.join(log_dir, "sample_humanization_result.csv")
     human = []
     with open(save_fpath, "a", encoding="UTF-8") as f:

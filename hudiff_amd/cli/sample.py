@@ -212,6 +212,7 @@ def main(argv=None):
     # re-sweeps until sample_number rows have been written (batch_size rows per pass)
     passes = 1 if args.similarity_search else max(1, -(-args.sample_number // args.batch_size))
     live = None
+    result_redrawn = None                                           # (--refine_rounds with --logp_fpath: positions every row redrew)
     if args.beam:
         # beam search: the W best rows of every input stand where the replicas stand, best first; all live ones are written
         beam = run_beam(model, jobs, args, "ab", logger)
@@ -236,10 +237,14 @@ def main(argv=None):
         forward_stats = {}
         more.update(apply_block_args(args, jobs, logger, forward_stats))
         more.update(apply_budget_args(args, jobs, logger))
+        if args.logp_fpath and "refine" in more:                    # the sidecar then names the positions every row redrew
+            more["return_redrawn"] = True
         result = sample_jobs(model, jobs, args.batch_size, args.seed, passes=passes, device_batch=args.device_batch,
                              dropout=args.dropout, q_noise=q_noise, **more)
         log_forward_stats(forward_stats, logger)
-        if args.logp_fpath:
+        if args.logp_fpath and "refine" in more:
+            result, result_logp, result_redrawn = result
+        elif args.logp_fpath:
             result, result_logp = result
     if rank != 0:
         return None
@@ -275,7 +280,9 @@ def main(argv=None):
                         left -= 1
     if args.logp_fpath:
         write_logp_csv(args.logp_fpath, [(job.name, p, r, len(job.loc), float(result_logp[j, p, r].astype(np.float64).sum()), (j, p, r) in chosen)
-                                         for j, job in enumerate(jobs) for p in range(result.shape[1]) for r in range(args.batch_size)])
+                                         + (() if result_redrawn is None else (int(result_redrawn[j, p, r]),))
+                                         for j, job in enumerate(jobs) for p in range(result.shape[1]) for r in range(args.batch_size)],
+                       redrawn=result_redrawn is not None)
     logger.info("Length did not equal list: {}".format([]))
     logger.info("Wrong idx: {}".format([]))
     # sample_identity.fa (trans_to_chain + save_pairs, sample.py:34-54): '{fa_version}human{i}' VH / VL pairs

@@ -120,6 +120,11 @@ struct Workspace {
     // distribution record (HD_RECORD_DIST): the 22 values of every (row, position) a forward drew or scored, [B, Tmax, 22].  Allocated by
     // the first session of the lane that asks, regrown like the beam's buffers.
     float* dist = nullptr; size_t dist_cap = 0;
+    // refinement rounds (hd_set_refine): T as the begin uploaded it [B] (refine_remask_k moves ws.T on; a restart puts it back), rounds
+    // opened so far [B], and first appended position / appended count of every round [B, rounds] (capacity B * REFINE_MAX_ROUNDS).
+    // Allocated by the first refinement session of the lane, regrown like the beam's buffers.  Such a session keeps the order0 / gallow0 /
+    // gbias0 copies of a confident one whatever its policy: the appended positions and the holes are taken back by a restart.
+    int32_t *rT0 = nullptr, *rdone = nullptr, *rstart = nullptr, *rcount = nullptr; size_t ref_capB = 0;
     uint8_t *enc_masks = nullptr, *conv_masks = nullptr; size_t enc_cap = 0, conv_cap = 0;
     std::vector<void*> owned;
 };
@@ -191,7 +196,8 @@ struct SessionOpts {
     bool budget = false;                             // mutation budget; a budgeted session always draws with the guided kernels (guide != GUIDE_NONE)
     float cmax = 0.f;                                // confidence threshold: 1 / tau (a kernel argument), 0 = none; such a session is confident and guided
     bool dist = false;                               // distribution record (HD_RECORD_DIST of the begin's flags, not an hd_set_*): the draw stores all 22 values
-    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget, cmax, dist); }
+    int rrounds = 0, rslots = 0; float rbelow = 0.f; // refinement rounds (hd_set_refine): rounds (0 = none), slots per round, the logp bound; such a session records
+    auto tied() const { return std::tie(mode, guide, temp, K, policy, trunc, tr.top_k, tr.top_p, tr.min_p, W, budget, cmax, dist, rrounds, rslots, rbelow); }
     bool operator==(const SessionOpts& o) const { return tied() == o.tied(); }
 };
 
@@ -210,9 +216,10 @@ struct StepKey {
     const int32_t *borigin = nullptr, *bmax = nullptr, *bn = nullptr;   // the budget buffers, when the session has one
     const int32_t *tfilled = nullptr, *tcnt = nullptr, *tfwd = nullptr; // the threshold buffers, when the session has one
     const float* dist = nullptr;                                        // the distribution record, when the session keeps one
+    const int32_t *rdone = nullptr, *rstart = nullptr, *rcount = nullptr;       // the refinement buffers, when the session has rounds
     auto tied() const {
         return std::tie(captured, B, no_prune, drop, Tmax, has_q, qptr, qB, qoff, kernels, o, gallow, gbias, borigin, bmax, bn, tfilled, tcnt, tfwd,
-                        dist);
+                        dist, rdone, rstart, rcount);
     }
     bool operator==(const StepKey& k) const { return tied() == k.tied(); }
 };
@@ -788,6 +795,22 @@ extern "C" HdStatus hd_set_budget(HdModel* m, const HdBudget* b) {
     k.origin.assign(b->origin, b->origin + (size_t)b->B * m->L);
     k.max_mut.assign(b->max_mutations, b->max_mutations + b->B);
     m->pending.budget = true;
+    return HD_OK;
+}
+
+// include/hudiff_hip.h "refinement rounds": the next begin takes them; rounds == 0 clears.
+extern "C" HdStatus hd_set_refine(HdModel* m, int32_t rounds, int32_t slots, float below) {
+    // (the values first: their checks need no handle)
+    if (rounds < 0 || rounds > REFINE_MAX_ROUNDS) return fail(HD_ERR_INVALID, "hd_set_refine: rounds = %d outside [0, %d]", rounds, REFINE_MAX_ROUNDS);
+    if (rounds > 0 && (slots < 1 || slots > REFINE_MAX_SLOTS))
+        return fail(HD_ERR_INVALID, "hd_set_refine: slots = %d outside [1, %d]", slots, REFINE_MAX_SLOTS);
+    if (rounds > 0 && !(below <= 0.f && std::isfinite(below)))      // (NaN fails every comparison)
+        return fail(HD_ERR_INVALID, "hd_set_refine: below = %g is not a finite value <= 0", (double)below);
+    if (!m) return fail(HD_ERR_INVALID, "hd_set_refine: null model");
+    if (m->in_session) return fail(HD_ERR_STATE, "hd_set_refine: a sampling session is open (the refinement belongs to the NEXT begin)");
+    m->pending.rrounds = rounds;
+    m->pending.rslots = rounds > 0 ? slots : 0;
+    m->pending.rbelow = rounds > 0 ? below + 0.f : 0.f;            // (-0 becomes +0: one key for one rule)
     return HD_OK;
 }
 
@@ -2051,11 +2074,25 @@ static HdStatus beam_step(HdModel* m, const Segs& sg, bool prune) {
     return HD_OK;
 }
 
+// Refinement rounds (hd_set_refine): the first launch of a step.  A row that has drawn its whole list appends the live positions it is
+// least sure about to its order and masks their slots; every other row leaves at once.  Does not advance the step.
+static HdStatus refine_remask(HdModel* m, const Segs& sg) {
+    HdModel::Lane& ln = cur(m);
+    Workspace& ws = ln.ws;
+    static_assert(SEL_THREADS >= 304, "refine_remask_k: one thread per slot of a row (max_len <= 304, hd_create)");
+    hipLaunchKernelGGL(refine_remask_k, dim3(sg.B), dim3(SEL_THREADS), 0, ln.stream, ws.order, ws.T, m->sTmax, m->s.K, ws.tokens, m->L, ws.logp,
+                       m->s.guide != GUIDE_NONE ? ws.gallow : nullptr, m->s.guide == GUIDE_ALLOW_BIAS ? ws.gbias : nullptr, ln.rs, m->s.rrounds,
+                       m->s.rslots, m->s.rbelow, ws.rdone, ws.rstart, ws.rcount);
+    HIP_TRY(hipGetLastError());
+    return HD_OK;
+}
+
 static HdStatus one_step(HdModel* m, const Segs& sg, int dm, const uint8_t* em, const uint8_t* cm) {
     // a block session (K > 1) visits K rows per sequence: the last attention block runs for every row, as with HD_NO_PRUNE; so does a
     // confident session at any K, whose selection needs the hidden row of every remaining slot
     const bool confident = m->s.policy == HD_SLOTS_CONFIDENT;
     const bool prune = !(m->sflags & HD_NO_PRUNE) && m->s.K == 1 && !confident;
+    if (m->s.rrounds > 0) HD_TRY(refine_remask(m, sg));  // a row whose list is used up re-masks its least likely slots: the forward sees them masked
     HD_TRY(forward_body(m, sg, dm, em, cm, prune));
     if (m->s.W > 0) return beam_step(m, sg, prune);  // (a beam session has K = 1 and the given order: sample_begin_impl)
     if (confident) HD_TRY(slot_choose(m, sg));
@@ -2094,6 +2131,19 @@ static HdStatus check_options(const HdModel* m, const BeginIn& in, const Session
         if (guided && o.temp == 0.f)
             return fail(HD_ERR_INVALID, "hd_sample_begin: a guide with temperature 0 (greedy decode) has no distribution for a beam to rank under");
         if (B % W != 0) return fail(HD_ERR_INVALID, "hd_sample_begin: %d rows are not whole groups of beam width %d", B, W);
+    }
+    if (o.rrounds > 0) {                             // refinement rounds: the device appends order positions to a sampling row
+        const char* fn = in.score ? "hd_score_begin" : "hd_sample_begin";
+        if (in.score) return fail(HD_ERR_UNSUPPORTED, "hd_score_begin: refinement rounds are set (hd_set_refine); a scoring session draws nothing to redraw");
+        if (W > 0) return fail(HD_ERR_UNSUPPORTED, "%s: refinement rounds with a beam width set (hd_set_beam): a beam row has no draw to repeat", fn);
+        if (o.cmax > 0.f)
+            return fail(HD_ERR_UNSUPPORTED, "%s: refinement rounds with a confidence threshold (hd_set_confidence): a threshold row keeps its own "
+                                            "progress, not the step the rounds are opened by", fn);
+        if (o.budget)
+            return fail(HD_ERR_UNSUPPORTED, "%s: refinement rounds with a mutation budget (hd_set_budget): a redrawn slot would be counted twice", fn);
+        if ((in.flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
+            return fail(HD_ERR_UNSUPPORTED, "%s: refinement rounds take generated dropout masks or none (injected masks are laid out per step of "
+                                            "the list as given)", fn);
     }
     if (confident && (in.flags & HD_DROPOUT_MASK) == HD_DROPOUT_INJECT)
         return fail(HD_ERR_UNSUPPORTED, "hd_sample_begin: injected dropout masks are laid out per step of a one-slot loop in the given order; a "
@@ -2149,6 +2199,13 @@ static HdStatus check_budget(const HdModel* m, const BeginIn& in, const SessionO
     return HD_OK;
 }
 
+// Order positions a row with T list entries can come to use under `rounds` refinement rounds of R slots at K slots per step.
+static int refine_capacity(int T, int rounds, int R, int K) {
+    int e = T;
+    for (int r = 0; r < rounds; ++r) e = (e + K - 1) / K * K + R;
+    return e;
+}
+
 // The order lists: ranges, repeats inside a group of K, the groups of a beam, the candidate set of a confident session.
 static HdStatus check_orders(const HdModel* m, const BeginIn& in, const SessionOpts& o) {
     const int B = in.B, Tmax = in.Tmax, K = o.K, W = o.W;
@@ -2178,18 +2235,30 @@ static HdStatus check_orders(const HdModel* m, const BeginIn& in, const SessionO
         if (!same) return fail(HD_ERR_INVALID, "hd_sample_begin: row %d differs from row %d, the first of its beam group (tokens, region, chain, order and T must be equal)", b, a);
     }
     // slot policy: the candidate list of a confident session is a set -- any of its slots may meet any other in one group
-    if (o.policy == HD_SLOTS_CONFIDENT) {
+    // refinement rounds: the list is a set as well -- a slot has ONE live position, and one thread of refine_remask_k owns it
+    if (o.policy == HD_SLOTS_CONFIDENT || o.rrounds > 0) {
         std::vector<int> seen((size_t)m->L);
         for (int b = 0; b < B; ++b) {
             std::fill(seen.begin(), seen.end(), -1);
             for (int t = 0; t < T[b]; ++t) {
                 const int s = order[(size_t)b * Tmax + t];
                 if (seen[s] >= 0)
-                    return fail(HD_ERR_INVALID, "order[%d,%d] = order[%d,%d] = %d: the candidate list of a confident session repeats a slot",
-                                b, seen[s], b, t, s);
+                    return fail(HD_ERR_INVALID, "order[%d,%d] = order[%d,%d] = %d: the %s repeats a slot", b, seen[s], b, t, s,
+                                o.policy == HD_SLOTS_CONFIDENT ? "candidate list of a confident session" : "list of a session with refinement rounds");
                 seen[s] = t;
             }
         }
+    }
+    // refinement rounds: every round appends at the next multiple of K, up to R positions -- Tmax must hold the worst case of every row
+    if (o.rrounds > 0) {
+        int need = 0, row = 0;
+        for (int b = 0; b < B; ++b) {
+            const int e = refine_capacity(T[b], o.rrounds, o.rslots, K);
+            if (e > need) { need = e; row = b; }
+        }
+        if (need > Tmax)
+            return fail(HD_ERR_INVALID, "hd_sample_begin: Tmax = %d cannot hold %d refinement round(s) of %d slot(s) at %d slot(s) per step: row %d "
+                                        "with T = %d needs Tmax >= %d", Tmax, o.rrounds, o.rslots, K, row, T[row], need);
     }
     return HD_OK;
 }
@@ -2284,6 +2353,21 @@ static HdStatus bufs_thresh(Workspace& ws, size_t nB, size_t nT, F&& f) {
 template <typename F>
 static HdStatus bufs_dist(Workspace& ws, size_t n, F&& f) {
     HD_TRY(f(&ws.dist, n));
+    return HD_OK;
+}
+// A session with refinement rounds: T as uploaded and rounds opened [B], start and count of every round [B, REFINE_MAX_ROUNDS].
+template <typename F>
+static HdStatus bufs_refine(Workspace& ws, size_t nB, F&& f) {
+    HD_TRY(f(&ws.rT0, nB)); HD_TRY(f(&ws.rdone, nB)); HD_TRY(f(&ws.rstart, nB * REFINE_MAX_ROUNDS)); HD_TRY(f(&ws.rcount, nB * REFINE_MAX_ROUNDS));
+    return HD_OK;
+}
+// Its state at the begin and at a restart: the caller's T, no round opened (start = -1, count = 0).
+static HdStatus refine_reset(HdModel::Lane& ln, int rounds) {
+    Workspace& ws = ln.ws;
+    HIP_TRY(hipMemcpyAsync(ws.T, ws.rT0, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+    HIP_TRY(hipMemsetAsync(ws.rdone, 0, (size_t)ln.B * sizeof(int32_t), ln.stream));
+    HIP_TRY(hipMemsetAsync(ws.rstart, 0xFF, (size_t)ln.B * rounds * sizeof(int32_t), ln.stream));
+    HIP_TRY(hipMemsetAsync(ws.rcount, 0, (size_t)ln.B * rounds * sizeof(int32_t), ln.stream));
     return HD_OK;
 }
 // Its state at the begin and at a restart: nothing filled, no forward run (fwd = -1 everywhere).
@@ -2381,12 +2465,21 @@ static HdStatus lane_begin(HdModel* m, const BeginIn& in, const SessionOpts& o, 
     }
     if (Tmax > 0) HIP_TRY(hipMemcpyAsync(ws.order, in.order + (size_t)off * Tmax, nT * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
     HIP_TRY(hipMemcpyAsync(ws.T, in.T + off, (size_t)Bl * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+    if (o.rrounds > 0) {                                 // the lane's rows start with the caller's T and no round opened
+        if ((size_t)Bl > ws.ref_capB) {
+            ws.ref_capB = 0;
+            HD_TRY(regrow(ln, [&](auto f) { return bufs_refine(ws, (size_t)Bl, f); }));
+            ws.ref_capB = (size_t)Bl;
+        }
+        HIP_TRY(hipMemcpyAsync(ws.rT0, ws.T, (size_t)Bl * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
+        HD_TRY(refine_reset(ln, o.rrounds));
+    }
     if (o.mode != DRAW_SAMPLE && Tmax > 0) {
         HIP_TRY(hipMemsetAsync(ws.logp, 0, nT * sizeof(float), ln.stream));
         if (in.score) HIP_TRY(hipMemcpyAsync(ws.target, target.data() + (size_t)off * Tmax, nT * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
     }
-    if (o.policy == HD_SLOTS_CONFIDENT && Tmax > 0) {    // what slot_select_k permutes, as uploaded: hd_sample_restart starts from the caller's list again
-        HIP_TRY(hipMemsetAsync(ws.conf, 0, nT * sizeof(float), ln.stream));        // (hd_sample_keys before the first forward reads zeros)
+    if ((o.policy == HD_SLOTS_CONFIDENT || o.rrounds > 0) && Tmax > 0) {    // what slot_select_k permutes and refine_remask_k appends to, as uploaded: hd_sample_restart starts from the caller's list again
+        if (o.policy == HD_SLOTS_CONFIDENT) HIP_TRY(hipMemsetAsync(ws.conf, 0, nT * sizeof(float), ln.stream));        // (hd_sample_keys before the first forward reads zeros)
         HIP_TRY(hipMemcpyAsync(ws.order0, ws.order, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (in.score) HIP_TRY(hipMemcpyAsync(ws.target0, ws.target, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
         if (guided) HIP_TRY(hipMemcpyAsync(ws.gallow0, ws.gallow, nT * sizeof(uint32_t), hipMemcpyDeviceToDevice, ln.stream));
@@ -2430,7 +2523,7 @@ static HdStatus sample_begin_impl(HdModel* m, BeginIn in, SessionOpts o, HdModel
     m->order_ready = false;
     m->count_ready = false;
     o.dist = (in.flags & HD_RECORD_DIST) != 0;       // the distribution record: from the flags, and its sampling session records logp too
-    o.mode = in.score ? DRAW_SCORE : ((in.flags & (HD_RECORD_LOGP | HD_RECORD_DIST)) || o.W > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records)
+    o.mode = in.score ? DRAW_SCORE : ((in.flags & (HD_RECORD_LOGP | HD_RECORD_DIST)) || o.W > 0 || o.rrounds > 0) ? DRAW_RECORD : DRAW_SAMPLE;      // (a beam session always records; so does one with refinement rounds, which are chosen from the record)
     // a truncated session draws with the guided kernels: without a guide of the caller's it gets the neutral one (every token allowed, no
     // bias, temperature 1), under which g_j == logit_j bit for bit
     // and so does a budgeted one: the budget rides in the guide argument of the guided kernels
@@ -2528,7 +2621,8 @@ extern "C" HdStatus hd_sample_restart(HdModel* m, uint64_t seed) {
             HIP_TRY(hipMemcpyAsync(ln.ws.bscore, m->beam_score0.data() + ln.row_off, (size_t)ln.B * sizeof(float), hipMemcpyHostToDevice, ln.stream));
             HIP_TRY(hipMemsetAsync(ln.ws.bparent, 0, (size_t)ln.B * (m->sTmax > 0 ? m->sTmax : 1) * sizeof(int32_t), ln.stream));
         }
-        if (m->s.policy == HD_SLOTS_CONFIDENT && m->sTmax > 0) {      // back to the caller's candidate list
+        if (m->s.rrounds > 0) HD_TRY(refine_reset(ln, m->s.rrounds));                                           // no round opened yet
+        if ((m->s.policy == HD_SLOTS_CONFIDENT || m->s.rrounds > 0) && m->sTmax > 0) {      // back to the caller's candidate list
             const size_t nT = (size_t)ln.B * m->sTmax;
             HIP_TRY(hipMemcpyAsync(ln.ws.order, ln.ws.order0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
             if (m->s.mode == DRAW_SCORE) HIP_TRY(hipMemcpyAsync(ln.ws.target, ln.ws.target0, nT * sizeof(int32_t), hipMemcpyDeviceToDevice, ln.stream));
@@ -2557,6 +2651,7 @@ static StepKey step_key(const HdModel* m, const HdModel::Lane& ln) {
     if (k.o.budget) { k.borigin = ln.ws.borigin; k.bmax = ln.ws.bmax; k.bn = ln.ws.bn; }
     if (k.o.cmax > 0.f) { k.tfilled = ln.ws.tfilled; k.tcnt = ln.ws.tcnt; k.tfwd = ln.ws.tfwd; }
     if (k.o.dist) k.dist = ln.ws.dist;
+    if (k.o.rrounds > 0) { k.rdone = ln.ws.rdone; k.rstart = ln.ws.rstart; k.rcount = ln.ws.rcount; }
     return k;
 }
 
@@ -2811,7 +2906,10 @@ extern "C" HdStatus hd_sample(HdModel* m, int32_t* tokens, const int32_t* region
                               const uint8_t* enc_masks, const uint8_t* conv_masks) {
     HD_TRY(hd_sample_begin(m, tokens, region, chain, order, T, B, Tmax, flags, seed, row0, q_noise, enc_masks, conv_masks));
     int tmax_eff = 0;
-    for (int b = 0; b < B; ++b) tmax_eff = T[b] > tmax_eff ? T[b] : tmax_eff;
+    for (int b = 0; b < B; ++b) {                     // (refinement rounds: the positions the row's rounds can come to use)
+        const int e = m->s.rrounds > 0 ? refine_capacity(T[b], m->s.rrounds, m->s.rslots, m->s.K) : T[b];
+        tmax_eff = e > tmax_eff ? e : tmax_eff;
+    }
     if (m->s.K > 1) {                                 // whole groups (or up to Tmax): what hd_sample_run takes in a block session
         tmax_eff = (tmax_eff + m->s.K - 1) / m->s.K * m->s.K;
         if (tmax_eff > Tmax) tmax_eff = Tmax;
@@ -2902,6 +3000,22 @@ extern "C" HdStatus hd_sample_order(HdModel* m, int32_t* order) {
         HIP_TRY(hipMemcpyAsync(order + (size_t)ln.row_off * m->sTmax, ln.ws.order, (size_t)ln.B * m->sTmax * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
     }
     return readback_done(m, "hd_sample_order", "order is");
+}
+
+// include/hudiff_hip.h "refinement rounds": T as the rounds have moved it on, and the first appended position / the count of every round.
+extern "C" HdStatus hd_refine_state(HdModel* m, int32_t* T_now, int32_t* round_start, int32_t* round_count) {
+    if (!m || (!m->in_session && !m->order_ready)) return fail(HD_ERR_STATE, "hd_refine_state: no session (open, or ended and not yet replaced)");
+    if (m->s.rrounds <= 0) return fail(HD_ERR_STATE, "hd_refine_state: the session has no refinement rounds (hd_set_refine)");
+    if (m->sB == 0) return HD_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t R = (size_t)m->s.rrounds;
+    for (int l = 0; l < m->nlanes; ++l) {            // lanes are contiguous row blocks: whole-batch row order
+        HdModel::Lane& ln = m->lane[l];
+        if (T_now) HIP_TRY(hipMemcpyAsync(T_now + ln.row_off, ln.ws.T, (size_t)ln.B * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+        if (round_start) HIP_TRY(hipMemcpyAsync(round_start + ln.row_off * R, ln.ws.rstart, ln.B * R * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+        if (round_count) HIP_TRY(hipMemcpyAsync(round_count + ln.row_off * R, ln.ws.rcount, ln.B * R * sizeof(int32_t), hipMemcpyDeviceToHost, ln.stream));
+    }
+    return readback_done(m, "hd_refine_state", "state is");
 }
 
 // include/hudiff_hip.h "confidence threshold": the progress of every row, the forward number of every position, and the keys of the

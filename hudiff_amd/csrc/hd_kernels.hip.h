@@ -2935,6 +2935,90 @@ __global__ void __launch_bounds__(SEL_THREADS) slot_select_k(int32_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// Refinement rounds (hd_set_refine, include/hudiff_hip.h "refinement rounds"): refine_remask_k is the FIRST launch of a step of such a
+// session, in front of the forward, one workgroup per row.  It reads rs->step and never advances it.  A row whose list is not used up
+// (step < T[b]) or whose rounds are all done leaves at once.  Otherwise the row opens a round: the LAST position of every slot in
+// order[b, 0:T[b]) is that slot's live position (an LDS maximum per slot; holes hold -1 and are skipped), a live position u is a
+// candidate iff logp[b, u] < below, candidates are ranked by (logp, u) ascending by counting in LDS -- a total order, so the ranks are a
+// permutation and the result is a function of the record alone -- and the first min(R, candidates) are APPENDED to the row's order at
+// base = the smallest multiple of K that is >= T[b]: order, the guide's entries of position u, tokens[b, slot] = 22, then T[b], the
+// round counter and the round's (start, count).  Positions in [old T[b], base) become holes (-1; K > 1 only; never drawn, the step is
+// already base).  The draw, the pruned tail and the selection kernels then run unchanged on the appended positions: they read order and
+// T from the device at every launch.  One thread per slot (L <= 304 <= SEL_THREADS); every read of the row is in front of the barrier
+// that precedes its first write; no global atomics, plain vector stores.
+// ------------------------------------------------------------------------------------------------
+constexpr int REFINE_MAX_ROUNDS = 16;
+constexpr int REFINE_MAX_SLOTS = 64;
+__global__ void __launch_bounds__(SEL_THREADS) refine_remask_k(int32_t* __restrict__ order, int32_t* __restrict__ T, int Tmax, int K,
+                                                     int32_t* __restrict__ tokens, int L, const float* __restrict__ logp,
+                                                     uint32_t* __restrict__ gallow, float* __restrict__ gbias,
+                                                     const RunState* __restrict__ rs, int rounds, int R, float below,
+                                                     int32_t* __restrict__ rounds_done, int32_t* __restrict__ round_start,
+                                                     int32_t* __restrict__ round_count) {
+    __shared__ int last[SEL_THREADS];                    // slot -> its last order position, -1: not in the list
+    __shared__ float key[SEL_THREADS];                   // slot -> logp of its live position
+    __shared__ int pos[SEL_THREADS];                     // slot -> its live position when that is a candidate, else -1
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int Tb = T[b];
+    const uint32_t step = __hip_atomic_load(&rs->step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (step < (uint32_t)Tb) return;                     // (the whole workgroup: the row still has positions to draw)
+    const int rd = rounds_done[b];
+    if (rd >= rounds) return;
+    const int base = (Tb + K - 1) / K * K;
+    const long p0 = (long)b * Tmax;
+    last[tid] = -1;
+    __syncthreads();
+    for (int t = tid; t < Tb; t += SEL_THREADS) {
+        const int s = order[p0 + t];
+        if (s >= 0 && s < L) atomicMax(&last[s], t);     // (LDS, integer maximum: the same value in any order)
+    }
+    __syncthreads();
+    const int u = tid < L ? last[tid] : -1;
+    float lp = 0.f;
+    bool cand = false;
+    if (u >= 0) { lp = logp[p0 + u]; cand = lp < below; }        // (a NaN never qualifies)
+    uint32_t ga = 0;
+    float gb[22];
+    if (cand) {
+        if (gallow) ga = gallow[p0 + u];
+        if (gbias) {
+#pragma unroll
+            for (int j = 0; j < 22; ++j) gb[j] = gbias[(p0 + u) * 22 + j];
+        }
+    }
+    key[tid] = lp;
+    pos[tid] = cand ? u : -1;
+    __syncthreads();
+    int r = 0, nc = 0;                                   // rank of this candidate, candidates of the row (every thread forms the same nc)
+    for (int v = 0; v < L; ++v) {
+        const int pv = pos[v];
+        if (pv < 0) continue;
+        const float kv = key[v];
+        nc += 1;
+        r += (kv < lp || (kv == lp && pv < u)) ? 1 : 0;
+    }
+    const int Rb = R < nc ? R : nc;
+    if (base + Rb > Tmax) return;                        // (the begin has checked the capacity of every row: never taken)
+    for (int t = Tb + tid; t < base; t += SEL_THREADS) order[p0 + t] = -1;
+    if (cand && r < Rb) {
+        const long d = p0 + base + r;
+        order[d] = tid;
+        if (gallow) gallow[d] = ga;
+        if (gbias) {
+#pragma unroll
+            for (int j = 0; j < 22; ++j) gbias[d * 22 + j] = gb[j];
+        }
+        tokens[(long)b * L + tid] = 22;
+    }
+    if (tid == 0) {
+        T[b] = base + Rb;
+        rounds_done[b] = rd + 1;
+        round_start[(long)b * rounds + rd] = base;
+        round_count[(long)b * rounds + rd] = Rb;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Beam search (hd_set_beam, include/hudiff_hip.h "beam search"): two launches take the place of the draw of a one-slot step.  A lane
 // holds whole groups of W consecutive rows; the rows of a group share order, T and everything but their tokens.
 //

@@ -17,6 +17,10 @@ draw; ``truncation_keep`` is its keep-set in float64, and ``guided_log_probs`` /
 
 A ``Budget`` (origin, max_mutations; include/hudiff_hip.h "mutation budget") caps the slots in which a row may differ from its origin;
 ``budget_walk`` is its rules 1 and 3 in numpy.
+
+Refinement rounds (include/hudiff_hip.h "refinement rounds"): ``refine_args`` checks a ``refine=dict(rounds=, slots=, below=)``,
+``refine_tcap`` is the order capacity such a session needs, ``refine_select`` the rule of a round in numpy, ``refine_live`` /
+``refine_fold`` read a record that is keyed by order position slot by slot.
 """
 from __future__ import annotations
 
@@ -336,6 +340,107 @@ def threshold_select(c32, K, cmax):
     chosen = rank[:cnt].astype(np.int64)
     rest = np.setdiff1d(np.arange(N), chosen)        # (sorted: the previous relative order)
     return chosen, cnt, np.concatenate([chosen, rest]).astype(np.int64)
+
+
+REFINE_MAX_ROUNDS, REFINE_MAX_SLOTS = 16, 64
+
+
+def refine_args(refine):
+    """A refinement as the library takes it (include/hudiff_hip.h "refinement rounds"): ``refine`` is None, or a mapping with ``rounds``
+    in [1, 16], ``slots`` in [1, 64] and optionally ``below``, a finite float <= 0 (default 0).  Returns None when there is nothing to
+    arm (None, or rounds == 0), else ``(rounds, slots, below)``; anything else is a ValueError."""
+    if refine is None:
+        return None
+    try:
+        unknown = set(refine) - {"rounds", "slots", "below"}
+        rounds, slots, below = refine["rounds"], refine.get("slots", 1), refine.get("below", 0.0)
+    except (TypeError, KeyError, AttributeError):
+        raise ValueError(f"refine must be a mapping with rounds, slots and optionally below, got {refine!r}") from None
+    if unknown:
+        raise ValueError(f"refine has unknown keys {sorted(unknown)}")
+    for name, v in (("rounds", rounds), ("slots", slots)):
+        if isinstance(v, (bool, float, str, bytes)) or v is None or int(v) != v:
+            raise ValueError(f"refine {name} must be an integer, got {v!r}")
+    rounds, slots = int(rounds), int(slots)
+    if rounds == 0:
+        return None
+    if not 1 <= rounds <= REFINE_MAX_ROUNDS:
+        raise ValueError(f"refine rounds must be in [0, {REFINE_MAX_ROUNDS}], got {rounds}")
+    if not 1 <= slots <= REFINE_MAX_SLOTS:
+        raise ValueError(f"refine slots must be in [1, {REFINE_MAX_SLOTS}], got {slots}")
+    if isinstance(below, (bool, str, bytes)) or below is None:
+        raise ValueError(f"refine below must be a finite number <= 0, got {below!r}")
+    below = float(below)
+    if not (np.isfinite(below) and below <= 0.0):
+        raise ValueError(f"refine below must be a finite number <= 0, got {below!r}")
+    return rounds, slots, float(np.float32(below))
+
+
+def refine_tcap(T, rounds, slots, K=1):
+    """Order positions a session with refinement rounds can come to use: with e = T, ``rounds`` times e = ceil(e / K) * K + slots; the
+    largest e over the rows of ``T`` (a number or an array).  The ``Tmax`` of such a session must be at least this."""
+    rounds, slots, K = int(rounds), int(slots), int(K)
+    if rounds < 0 or slots < 0 or K < 1:
+        raise ValueError(f"refine_tcap needs rounds >= 0, slots >= 0 and K >= 1, got {rounds}, {slots}, {K}")
+    e = np.asarray(T, dtype=np.int64).reshape(-1)
+    for _ in range(rounds):
+        e = (e + K - 1) // K * K + slots
+    return int(e.max()) if e.size else 0
+
+
+def refine_live(order, T_now):
+    """bool, the shape of ``order`` ([Tmax] or [B, Tmax]): position t is LIVE iff t < T_now, order[t] is not a hole (-1) and no later
+    position below T_now holds the same slot -- the position whose draw is the row's final token at that slot."""
+    order = np.asarray(order)
+    one = order.ndim == 1
+    o2 = order.reshape(1, -1) if one else order
+    Tn = np.asarray(T_now, dtype=np.int64).reshape(-1)
+    if o2.ndim != 2 or Tn.shape != (o2.shape[0],):
+        raise ValueError(f"order must be [Tmax] or [B, Tmax] and T_now one entry per row, got {order.shape}, {Tn.shape}")
+    live = np.zeros(o2.shape, dtype=bool)
+    for b in range(o2.shape[0]):
+        seen = set()
+        for t in range(int(Tn[b]) - 1, -1, -1):
+            s = int(o2[b, t])
+            if s >= 0 and s not in seen:
+                seen.add(s)
+                live[b, t] = True
+    return live[0] if one else live
+
+
+def refine_select(logp, order, T_now, slots, below=0.0):
+    """The rule of a refinement round for ONE row, in numpy (include/hudiff_hip.h "refinement rounds", 1 and 2): ``logp`` float32
+    [Tmax] and ``order`` int [Tmax] are the row's record and order as they stand, ``T_now`` its positions in use.  The live positions
+    with logp < below (a float32 compare; NaN never qualifies) are ranked by (logp, position) ascending and the first
+    min(slots, candidates) are chosen.  Returns ``(slot, position)``: int64 [R_b] each, in rank order -- the round appends ``slot`` to
+    the order at base, base + 1, ... and takes the guide's entries from ``position``."""
+    lp = np.asarray(logp, dtype=np.float32).reshape(-1)
+    od = np.asarray(order).reshape(-1)
+    if lp.shape != od.shape:
+        raise ValueError(f"logp and order must have one shape, got {lp.shape}, {od.shape}")
+    T_now, slots = int(T_now), int(slots)
+    if not 0 <= T_now <= od.size or slots < 1:
+        raise ValueError(f"refine_select needs 0 <= T_now <= {od.size} and slots >= 1, got {T_now}, {slots}")
+    u = np.flatnonzero(refine_live(od, [T_now]))
+    with np.errstate(invalid="ignore"):
+        u = u[lp[u] < np.float32(below)]
+    u = u[np.argsort(lp[u], kind="stable")][:slots]  # (u ascends, and a stable sort keeps that among equal logp)
+    return od[u].astype(np.int64), u.astype(np.int64)
+
+
+def refine_fold(order, T_now, values, L=None):
+    """Per-slot values of a refined session: ``values`` [B, Tmax, ...] is keyed by order position (``sample_logp()``,
+    ``sample_dist()``, ...); out[b, s, ...] = values[b, u, ...] at the live position u of slot s, 0 for a slot that is not in the
+    row's list.  ``L``: slots per row (default: the largest slot in ``order`` + 1)."""
+    order, values = np.asarray(order), np.asarray(values)
+    if order.ndim != 2 or values.shape[:2] != order.shape:
+        raise ValueError(f"order must be [B, Tmax] and values [B, Tmax, ...], got {order.shape}, {values.shape}")
+    live = refine_live(order, T_now)
+    L = (int(order.max()) + 1 if order.size else 0) if L is None else int(L)
+    out = np.zeros((order.shape[0], max(L, 0)) + values.shape[2:], dtype=values.dtype)
+    b, t = np.nonzero(live)
+    out[b, order[b, t]] = values[b, t]
+    return out
 
 
 def beam_select(cand, width):

@@ -375,10 +375,43 @@ class _Denoiser:
         L.check(self._lib.hd_sample_run_to_end(self._h, int(chunk), C.byref(n)))
         return int(n.value)
 
-    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None, budget=None, confidence=None):
+    # -- refinement rounds -----------------------------------------------------------------------
+    def set_refine(self, rounds, slots=1, below=0.0):
+        """hd_set_refine: ``rounds`` in [1, 16] refinement rounds (0 clears) of ``slots`` in [1, 64] slots each, redrawing the live
+        positions whose recorded logp is < ``below`` (finite, <= 0), for the NEXT sample / sample_begin on this handle, which consumes
+        it whether it succeeds or fails (include/hudiff_hip.h "refinement rounds")."""
+        L.check(self._lib.hd_set_refine(self._h, int(rounds), int(slots), float(below)))
+
+    def refine_state(self, B=None, rounds=None):
+        """hd_refine_state: ``(T_now int32 [B], round_start int32 [B, rounds], round_count int32 [B, rounds])`` of the open session
+        with refinement rounds, or of the last one: the order positions every row has come to use, and the first appended position
+        (-1: not opened) and the number of slots of every round."""
+        B = self._session_B if B is None else B
+        rounds = getattr(self, "_session_rounds", 0) if rounds is None else int(rounds)
+        T_now = np.zeros(B, dtype=np.int32)
+        start = np.full((B, rounds), -1, dtype=np.int32)
+        count = np.zeros((B, rounds), dtype=np.int32)
+        L.check(self._lib.hd_refine_state(self._h, L.ptr(T_now, C.c_int32), L.ptr(start, C.c_int32), L.ptr(count, C.c_int32)))
+        return T_now, start, count
+
+    def _refine_pad(self, order, T, refine, slots_per_step):
+        """``refine`` checked, and ``order`` padded with zeros to the positions its rounds can come to use (guide.refine_tcap)."""
+        from .guide import refine_args, refine_tcap
+        ra = refine_args(refine)
+        if ra is None:
+            return order, None
+        order = np.asarray(order)
+        if order.ndim == 2:
+            need = refine_tcap(np.asarray(T).reshape(-1), ra[0], ra[1], int(slots_per_step))
+            if order.shape[1] < need:
+                order = np.concatenate([order, np.zeros((order.shape[0], need - order.shape[1]), dtype=order.dtype)], axis=1)
+        return order, ra
+
+    def _arm(self, guide, B, slots_per_step, slot_policy="given", truncation=None, budget=None, confidence=None, refine=None):
         """What the next begin consumes: the block size (the library is told only when it is not 1), the slot policy (told only when
         it is not "given"), the truncation (told only when it cuts something), the budget (told only when there is one), the
-        confidence threshold (told only when there is one) and the guide."""
+        confidence threshold (told only when there is one), the refinement (``refine``: None or the checked (rounds, slots, below);
+        told only when there is one) and the guide."""
         policy = self._policy_id(slot_policy)
         block = int(slots_per_step) != 1
         trunc = truncation is not None and not truncation.neutral
@@ -395,9 +428,13 @@ class _Denoiser:
                 self.set_truncation(truncation)
             if budget is not None:
                 self.set_budget(budget, B)
+            if refine is not None:
+                self.set_refine(*refine)
             if guide is not None:
                 self.set_guide(guide, B)
         except Exception:
+            if refine is not None:
+                self._lib.hd_set_refine(self._h, 0, 0, 0.0)
             if block:
                 self.set_slots_per_step(1)           # (no begin will follow to consume it)
             if policy != L.HD_SLOTS_GIVEN:
@@ -412,7 +449,7 @@ class _Denoiser:
 
     def sample(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, return_logp=False, guide=None, slots_per_step=1,
-               slot_policy="given", truncation=None, budget=None, confidence=None, record_dist=False):
+               slot_policy="given", truncation=None, budget=None, confidence=None, record_dist=False, refine=None):
         """Run the T-step loop (sample.py:499-513) for B independent rows; returns the filled tokens.
 
         ``guide``: a hudiff_amd.guide.Guide (allowed residues per slot, logit bias, temperature) for this call only.
@@ -444,12 +481,20 @@ class _Denoiser:
 
         ``record_dist``: the session keeps the whole 22-token distribution of every draw (HD_RECORD_DIST, include/hudiff_hip.h
         "distribution record") and records logp too; ``sample_dist()`` / ``sample_logp()`` afterwards return them.  The tokens are the
-        same with and without it."""
+        same with and without it.
+
+        ``refine``: ``dict(rounds=, slots=, below=0.0)`` for this call only -- after a row has drawn its whole list, its ``slots``
+        least likely live positions with logp < ``below`` are masked again and redrawn with everything else as context, ``rounds``
+        times (include/hudiff_hip.h "refinement rounds").  The session records; ``order`` is padded to ``guide.refine_tcap`` positions
+        (a ``q_noise`` must have that many), and ``sample_logp()`` / ``sample_order()`` / ``refine_state()`` afterwards have that
+        width.  None = none."""
+        order, ra = self._refine_pad(order, T, refine, slots_per_step)
         tok, reg, chn, order, T, B, Tmax, q, em, cm, was_torch = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
         out = tok.copy()
-        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence, ra)
         self._session_B, self._session_Tmax = B, Tmax
+        self._session_rounds = ra[0] if ra else 0
         L.check(self._lib.hd_sample(self._h, L.ptr(out, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                     L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                     self._flags(dropout, graph, prune, lanes, bool(return_logp), bool(record_dist)), int(seed), int(row0), L.ptr(q, C.c_float),
@@ -698,10 +743,14 @@ class _Denoiser:
 
     def sample_begin(self, tokens, region, chain, order, T, *, seed=0, row0=0, q_noise=None, dropout="faithful",
                      enc_masks=None, conv_masks=None, graph=True, prune=True, lanes=2, record_logp=False, guide=None, slots_per_step=1,
-                     slot_policy="given", truncation=None, budget=None, confidence=None, record_dist=False):
+                     slot_policy="given", truncation=None, budget=None, confidence=None, record_dist=False, refine=None):
+        """hd_sample_begin with what ``sample`` takes.  ``refine``: as there -- ``order`` is padded to ``guide.refine_tcap`` positions,
+        which is then the session's Tmax (``sample_run`` takes positions up to it)."""
+        order, ra = self._refine_pad(order, T, refine, slots_per_step)
         tok, reg, chn, order, T, B, Tmax, q, em, cm, _ = self._sample_args(
             tokens, region, chain, order, T, q_noise, enc_masks, conv_masks)
-        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence)
+        self._arm(guide, B, slots_per_step, slot_policy, truncation, budget, confidence, ra)
+        self._session_rounds = ra[0] if ra else 0
         L.check(self._lib.hd_sample_begin(self._h, L.ptr(tok, C.c_int32), L.ptr(reg, C.c_int32), L.ptr(chn, C.c_int32),
                                           L.ptr(order, C.c_int32), L.ptr(T, C.c_int32), B, Tmax,
                                           self._flags(dropout, graph, prune, lanes, bool(record_logp), bool(record_dist)), int(seed), int(row0), L.ptr(q, C.c_float),

@@ -59,7 +59,8 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
                 device_batch: int = 256, dropout: str = "faithful", q_noise=None, all_ranks: bool = False,
                 job_ids: Optional[Sequence[int]] = None, return_logp: bool = False, temperature: float = 1.0, slots_per_step: int = 1,
                 slot_policy: str = "given", return_order: bool = False, truncation=None, max_mutations: Optional[int] = None,
-                confidence: Optional[float] = None, forward_stats: Optional[dict] = None):
+                confidence: Optional[float] = None, forward_stats: Optional[dict] = None, refine: Optional[dict] = None,
+                return_redrawn: bool = False):
     """Sample ``replicas`` rows per job; returns int32 [len(jobs), passes, replicas, L] on rank 0 (every rank
     when single-process or ``all_ranks``).  ``passes`` > 1 re-runs the loop over the already filled tokens, which is what the
     reference's ``while sample_number > 0`` loop does (sample.py:499, nanosample.py:316).
@@ -90,8 +91,19 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     calls into the library are exactly today's.  ``forward_stats``: a dict that then receives, summed over this rank's rows with
     slots to fill, ``rows``, ``forwards`` (their total) and ``max`` (the most any row needed).
 
-    ``return_order``: also returns (last) int32 [len(jobs), passes, replicas, Tmax], the order each row took (model.sample_order;
+    ``refine``: ``dict(rounds=, slots=, below=0.0)``, refinement rounds (model.sample): after a row has drawn its whole ``loc``, its
+    least likely slots are masked again and redrawn with everything else as context, anew in every pass; None passes nothing on and
+    the calls into the library are exactly today's.  Tmax of the returned arrays is then ``guide.refine_tcap`` of the longest
+    ``loc``, and the returned log-probabilities are those of the LIVE positions only (the draw that is the row's final token at its
+    slot; 0 elsewhere), so a row's sum is the log-probability of what it ended with, each slot under the context it was last drawn
+    in.  ``return_redrawn``: also returns (last) int32 [len(jobs), passes, replicas], the number of slots each row redrew.
+
+    ``return_order``: also returns int32 [len(jobs), passes, replicas, Tmax], the order each row took (model.sample_order;
     under "given" the order it was handed), gathered like the log-probabilities."""
+    from .guide import refine_args, refine_live, refine_tcap
+    ra = refine_args(refine)
+    if return_redrawn and ra is None:
+        raise ValueError("return_redrawn needs refine")
     if slot_policy not in ("given", "confident"):
         raise ValueError(f"slot_policy must be 'given' or 'confident', got {slot_policy!r}")
     guided = float(temperature) != 1.0 or any(j.guide is not None for j in jobs)
@@ -101,9 +113,14 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     lo, hi = D.shard_bounds(n_rows, rank, world)
     is_ab = model.kind == "ab"
     Tmax = max([len(j.loc) for j in jobs] + [1])
+    if ra is not None:                                           # the positions the rounds can come to use
+        Tmax = refine_tcap([len(j.loc) for j in jobs] + [1], ra[0], ra[1], int(slots_per_step))
     out = np.zeros((passes, hi - lo, L), np.int32)
     lp = np.zeros((passes, hi - lo, Tmax), np.float32) if return_logp else None
+    redrawn = np.zeros((passes, hi - lo, 1), np.int32) if return_redrawn else None
     more = {"return_logp": True} if return_logp else {}
+    if ra is not None:
+        more["refine"] = dict(rounds=ra[0], slots=ra[1], below=ra[2])
     if int(slots_per_step) != 1:
         more["slots_per_step"] = int(slots_per_step)
     if slot_policy != "given":
@@ -141,6 +158,13 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
             if return_logp:
                 tok, lp[p, s - lo:e - lo] = tok
             out[p, s - lo:e - lo] = tok
+            if ra is not None and (return_logp or return_redrawn):
+                T_now, _, count = model.refine_state(len(jb), ra[0])
+                live = refine_live(model.sample_order(len(jb), Tmax), T_now)
+                if return_logp:
+                    lp[p, s - lo:e - lo] = np.where(live, lp[p, s - lo:e - lo], 0.0)
+                if return_redrawn:                                   # (a redrawn slot's live position is an appended one)
+                    redrawn[p, s - lo:e - lo, 0] = (live & (np.arange(Tmax)[None, :] >= T[:, None])).sum(axis=1)
             if return_order:
                 od[p, s - lo:e - lo] = model.sample_order(len(jb), Tmax)
             if thresh and forward_stats is not None:
@@ -152,8 +176,9 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
     # (the float32 bits of the log-probabilities travel as int32 through the same gather)
     gathered_lp = [D.gather_rows(lp[p].view(np.int32), n_rows, Tmax, all_ranks) for p in range(passes)] if return_logp else None
     gathered_od = [D.gather_rows(od[p], n_rows, Tmax, all_ranks) for p in range(passes)] if return_order else None
+    gathered_rd = [D.gather_rows(redrawn[p], n_rows, 1, all_ranks) for p in range(passes)] if return_redrawn else None
     if gathered[0] is None:
-        res = (None,) + ((None,) if return_logp else ()) + ((None,) if return_order else ())
+        res = (None,) + ((None,) if return_logp else ()) + ((None,) if return_order else ()) + ((None,) if return_redrawn else ())
         return res if len(res) > 1 else None
     tokens = np.stack(gathered, axis=0).reshape(passes, len(jobs), replicas, L).transpose(1, 0, 2, 3)
     res = (tokens,)
@@ -162,6 +187,8 @@ def sample_jobs(model, jobs: Sequence[Job], replicas: int, seed: int, *, passes:
         res += (logp.reshape(passes, len(jobs), replicas, Tmax).transpose(1, 0, 2, 3),)
     if return_order:
         res += (np.stack(gathered_od, axis=0).astype(np.int32).reshape(passes, len(jobs), replicas, Tmax).transpose(1, 0, 2, 3),)
+    if return_redrawn:
+        res += (np.stack(gathered_rd, axis=0).astype(np.int32).reshape(passes, len(jobs), replicas).transpose(1, 0, 2),)
     return res if len(res) > 1 else tokens
 
 
@@ -264,7 +291,8 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
                            device_batch: int = 256, dropout: str = "faithful", log=None, q_noise=None,
                            logp_records: Optional[list] = None, temperature: float = 1.0, slots_per_step: int = 1,
                            slot_policy: str = "given", truncation=None, max_mutations: Optional[int] = None,
-                           confidence: Optional[float] = None, forward_stats: Optional[dict] = None) -> List[List[np.ndarray]]:
+                           confidence: Optional[float] = None, forward_stats: Optional[dict] = None,
+                           refine: Optional[dict] = None) -> List[List[np.ndarray]]:
     """The nanobody sampler's accept / re-sweep loop (nanobody_scripts/nanosample.py:316-353), batched.
 
     Per input sequence the reference keeps ``sample_number`` (rows still wanted) and ``try_num``: while both are
@@ -285,7 +313,12 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
     ``max_mutations``: as in ``sample_jobs``; every sweep redraws every sampled slot and counts from 0, so every row written differs from
     its job's ``origin`` in at most that many of them.
 
-    ``confidence``, ``forward_stats``: as in ``sample_jobs``, for every sweep."""
+    ``confidence``, ``forward_stats``: as in ``sample_jobs``, for every sweep.
+
+    ``refine``: as in ``sample_jobs``, for every sweep; a record of ``logp_records`` then has a seventh field, the number of slots the
+    row redrew, and its logp is that of the live positions."""
+    from .guide import refine_args
+    refined = refine_args(refine) is not None
     state = [{"left": want, "tries": tries, "tokens": None, "out": []} for _ in jobs]
     active = [j for j in range(len(jobs)) if want > 0 and tries > 0]
     sweep = 0
@@ -309,10 +342,14 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
         if confidence is not None and float(confidence) != 0.0:
             more["confidence"] = confidence
             more["forward_stats"] = forward_stats
+        if refined:
+            more["refine"] = refine
+            more["return_redrawn"] = logp_records is not None
         res = sample_jobs(model, sub, replicas, seed + 1000003 * sweep, device_batch=device_batch, dropout=dropout,
                           all_ranks=True, job_ids=active, q_noise=q_noise if sweep == 0 else None, **more)
         if logp_records is not None:
-            res, res_lp = res
+            res_rd = res[2] if refined else None
+            res, res_lp = res[0], res[1]
         still = []
         for a, j in enumerate(active):
             st = state[j]
@@ -335,7 +372,8 @@ def sample_jobs_with_retry(model, jobs: Sequence[Job], replicas: int, seed: int,
                 st["tries"] -= 1
             if logp_records is not None:
                 for r in range(res.shape[2]):
-                    logp_records.append((j, sweep, r, len(jobs[j].loc), float(res_lp[a, 0, r].astype(np.float64).sum()), int(r in chosen)))
+                    logp_records.append((j, sweep, r, len(jobs[j].loc), float(res_lp[a, 0, r].astype(np.float64).sum()), int(r in chosen))
+                                        + ((int(res_rd[a, 0, r]),) if refined else ()))
             if st["left"] > 0 and st["tries"] > 0:
                 still.append(j)
         active = still

@@ -63,8 +63,8 @@ extern "C" {
                                  hd_sample_order; truncated sampling added hd_set_truncation and the struct HdTruncation; beam search added hd_set_beam and
                                  hd_beam_state; the mutation budget added hd_set_budget, hd_mutation_count and the struct HdBudget; the confidence
                                  threshold added hd_set_confidence, hd_sample_run_to_end, hd_sample_progress, hd_sample_forwards and hd_sample_keys; the
-                                 distribution record added hd_sample_dist and the flag HD_RECORD_DIST -- entry points only, so the version is
-                                 unchanged */
+                                 distribution record added hd_sample_dist and the flag HD_RECORD_DIST; refinement rounds added hd_set_refine and
+                                 hd_refine_state -- entry points only, so the version is unchanged */
 
 typedef enum HdStatus {
     HD_OK = 0,
@@ -540,6 +540,52 @@ HdStatus hd_sample_keys(HdModel* m, float* conf /* [B, Tmax] */);
  *
  * The flag with a beam width pending (hd_set_beam) -> HD_ERR_UNSUPPORTED: a beam session has its candidate table (hd_beam_state). */
 HdStatus hd_sample_dist(HdModel* m, float* dist /* [B, Tmax, 22] */);
+
+/* ---- refinement rounds ----------------------------------------------------------------------------
+ * A sampling session may carry a refinement (rounds, R, below): after a row has drawn its whole list, the slots it was least sure about
+ * are masked again and redrawn with everything else as context (mask-predict), `rounds` times.  rounds in [1, 16], R in [1, 64] slots per
+ * round, below a finite float <= 0.  Such a session always records (as under HD_RECORD_LOGP); the tokens of its first pass are those of the
+ * same session without refinement, bit for bit.
+ *
+ * A round is nothing but the device APPENDING order positions to a row.  State per row: T_now[b] (T[b] at the begin) and
+ * rounds_done[b] (0).  At the start of every step, before the forward, with s the step (an order position; a multiple of K), a row with
+ * s >= T_now[b] and rounds_done[b] < rounds opens a round:
+ *   1. for every slot in order[b, 0:T_now[b]) (holes excluded, see 4) its LIVE position u is the last position holding that slot; a live
+ *      position is a candidate iff logp[b, u] < below, compared on the recorded fp32 value (logp == 0 never qualifies at below == 0);
+ *   2. candidates are ranked by (logp[b, u], u) ascending -- least likely first, ties by position -- and the first
+ *      R_b = min(R, candidates) are chosen;
+ *   3. base = the smallest multiple of K that is >= T_now[b] (= s when the steps are run in sequence).  For j < R_b:
+ *      order[b, base + j] = the slot of rank j; the guide's entries of position base + j = those of position u; tokens[b, slot] = 22.
+ *      Then T_now[b] = base + R_b, rounds_done[b] += 1, round_start[b, r] = base, round_count[b, r] = R_b.  A round with R_b == 0 is
+ *      counted and appends nothing (every later round of that row is then empty too: its record does not change);
+ *   4. positions in [old T_now[b], base) exist only when K > 1: their order becomes -1 ("holes").  They are never drawn (the step is
+ *      already base) and their logp and dist entries keep their initial zeros.
+ * Everything keyed by order position keeps that key: the Philox counter word of the draw, q_noise[t, row, :], logp[b, t], dist[b, t, :],
+ * and generated dropout masks, keyed by the forward's first position.  Under the confident policy the selection permutes
+ * [min(s, T_now), T_now) as it always does, so the appended positions are filled surest first.  The row's final token at a slot is the
+ * one written at its live position; logp at earlier positions of that slot remains as history.  All of it runs on the device inside the
+ * captured step (one launch in front of the forward); nothing is read back; a session repeats bit for bit.
+ *
+ * Capacity: the caller's Tmax must hold the worst case.  With e = T[b], repeat `rounds` times e = ceil(e / K) * K + R; the begin requires
+ * e <= Tmax for every row, otherwise HD_ERR_INVALID (the message names the Tmax needed).  No buffer changes shape; hd_sample_run(t0, t1)
+ * keeps taking order positions up to Tmax, and hd_sample runs up to the largest e.
+ *
+ * The same result can be had by chaining sessions from the host: for a round, a given-order session on the re-masked tokens whose order
+ * holds the chosen slots at [base, base + R_b), run over those positions, draws the same tokens and records the same logp and dist bit
+ * for bit (same K, noise key, guide, dropout mode).
+ *
+ * Lifetime: as the block size -- one-shot: the NEXT hd_sample_begin / hd_sample consumes it whether it succeeds or fails;
+ * hd_sample_restart and the guards' repeats keep it and put T, order, the guide's entries and the counters back; hd_forward neither uses
+ * nor clears it.  hd_set_refine: rounds == 0 clears; a NULL handle, rounds outside [0, 16], slots outside [1, 64], or a below that is
+ * NaN, infinite or > 0 -> HD_ERR_INVALID (the values are looked at before the handle); inside an open session -> HD_ERR_STATE.  At the begin: a beam width, a confidence threshold, a
+ * mutation budget, HD_DROPOUT_INJECT, or hd_score_begin / hd_score -> HD_ERR_UNSUPPORTED; a row whose order[b, 0:T[b]] repeats a slot
+ * (a slot has ONE live position), or a Tmax below the capacity -> HD_ERR_INVALID.
+ *
+ * hd_refine_state copies T_now [B], round_start [B, rounds] (-1 for a round not opened) and round_count [B, rounds] out (each pointer
+ * may be NULL), rows in whole-batch order whatever the lane split.  Legal where hd_sample_order is; a session without refinement ->
+ * HD_ERR_STATE. */
+HdStatus hd_set_refine(HdModel* m, int32_t rounds, int32_t slots, float below);   /* rounds == 0 clears */
+HdStatus hd_refine_state(HdModel* m, int32_t* T_now /* [B] */, int32_t* round_start /* [B, rounds] */, int32_t* round_count /* [B, rounds] */);
 
 /* ---- measurement helpers ------------------------------------------------------------------------
  * hd_sample_run brackets the steps it enqueues with HIP events on the handle's stream;
